@@ -15,11 +15,14 @@ Workloads (BASELINE.json configs; --config picks one, the default follows --gpus
   5  one independent 129.6 MS/s front end per GPU (sig_gen seed = rank + 1), 1024 mixed channels each,
      no RCCL in the data path ("replicas only")
 
-Timing: after W warm-up steps, ONE region of exactly K steps is timed between device synchronisations
-(barrier across ranks on both sides) and reported as drained_k_step_region; it also sizes `reps`.  The
-headline is the steady state: `reps` back-to-back repetitions of the K-step loop (reps*K blocks, no drain in
-between) form one timed region, bracketed the same way; `regions` of them cover --min-seconds and the MEDIAN
-(max over ranks each) gives ms_per_step and value.  So the figure does not depend on how small K is.
+Timing: after W warm-up steps, ONE region of exactly K = --steps steps is timed between device synchronisations
+(barrier across ranks on both sides, max over ranks): ms_per_step = its time / K, pipeline fill and drain included
+(a K of a few seconds' worth of steps amortises them).
+
+--dump-outputs DIR: after the timed steps, what the timed path computed in its LAST step -- the block's spectrum and
+every channel's output, as a caller receives them -- goes to DIR/<name>.npy in float32 (complex as a trailing
+re/im axis; at most 64 MB in all, larger arrays as a fixed seeded sample of their rows).  The inputs depend on the
+arguments only, so two builds can be compared output for output.
 
 metric: channels sustained at the input rate = channel-blocks per second / 50 blocks/s
 (real-time-equivalent channels of the benchmarked configuration).  The c_rt object is the literal
@@ -32,7 +35,6 @@ import ctypes
 import json
 import os
 import socket
-import statistics
 import sys
 import threading
 import time
@@ -943,6 +945,31 @@ def _clean(x, sig=6):
     return x
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, seed=0):
+    """Write arrays (name -> ndarray, rows along the first axis) as dirname/<name>.npy in float32, complex values as a trailing
+    re/im axis.  Together they stay under DUMP_MAX_BYTES: an array over its equal share is replaced by a fixed, seeded sample of its
+    rows (sorted), whose indices go to <name>_rows.npy (float64).  Returns {name: {"shape": [...], "rows": total rows, "sampled": bool}}."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays))
+    meta = {}
+    for k, (name, a) in enumerate(sorted(arrays.items())):
+        a = np.asarray(a)
+        f = np.stack([a.real, a.imag], axis=-1).astype(np.float32) if np.iscomplexobj(a) else a.astype(np.float32)
+        row_bytes = max(1, f[:1].nbytes)
+        keep = f.shape[0] if f.nbytes <= share else max(1, (share - 4096) // (row_bytes + 8))
+        sampled = keep < f.shape[0]
+        if sampled:
+            rows = np.sort(np.random.default_rng(seed + k).choice(f.shape[0], keep, replace=False))
+            f = f[rows]
+            np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(f))
+        meta[name] = {"shape": list(f.shape), "rows": int(a.shape[0]), "sampled": bool(sampled)}
+    return meta
+
+
 def _pick(d, *keys):
     return {k: d[k] for k in keys if d is not None and k in d} if d else None
 
@@ -954,8 +981,7 @@ def headline(out, detail_path):
     h = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                              "vs_baseline", "dtype", "data")}
     h["config"] = _pick(out["config"], "workload", "baseline_config", "channels_total", "P", "olen", "N", "L", "M", "plan", "lanes", "value_is")
-    h.update(_pick(out, "reps", "regions", "ms_per_step_min", "ms_per_step_max", "drained_k_step_region_ms_per_step", "blocks_per_s",
-                   "step_algorithmic_GBps", "exchange_mode"))
+    h.update(_pick(out, "blocks_per_s", "step_algorithmic_GBps", "exchange_mode"))
     if out.get("legs"):
         h["legs"] = {k: _pick(v, "ms_per_step", "value") for k, v in out["legs"].items()}
     if roof:
@@ -1019,7 +1045,8 @@ def self_spawn(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush(); sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    import subprocess
+    raise SystemExit(subprocess.run(cmd).returncode)          # a fresh child: this process has touched the HIP runtime
 
 
 def main():
@@ -1033,7 +1060,10 @@ def main():
                          "over RCCL, every rank transforms) | replicate (no collective)")
     ap.add_argument("--channels", type=int, default=0, help="channels per GPU (default: the config's)")
     ap.add_argument("--plan", default="", help="forward plan override, e.g. 144x100x225")
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="keep repeating the K-step region until this much is measured")
+    # (older scripts pass --min-seconds: accepted and ignored -- the timed region is exactly --steps steps)
+    ap.add_argument("--min-seconds", type=float, default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the spectrum and the channel outputs of the last timed step to DIR/<name>.npy (float32, <= 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--graph", action="store_true", help="replay one hipGraph per ring cycle instead of eager launches (N=1)")
     ap.add_argument("--no-crt", action="store_true", help="skip the C_rt leg (one large bank, every block inside 20 ms)")
@@ -1056,6 +1086,8 @@ def main():
                     help="iteration mode: the headline and the roofline object only (no C_rt ladder, PCIe probes, 8f chain, drop-in or CPU legs): "
                          "< 30 s of GPU time.  The driver's command (no --quick) keeps the full line")
     args = ap.parse_args()
+    if args.min_seconds is not None:
+        print("bench.py: --min-seconds is ignored: the timed region is exactly --steps steps", file=sys.stderr)
     if args.quick:
         args.no_crt = args.no_next_rows = args.no_dropin = args.no_dropin_paced = args.no_crt_pcie = args.no_cpu_baseline = True
     if args.gpus < 1 or args.steps < 1 or args.warmup < 0:
@@ -1211,31 +1243,18 @@ def main():
         return max_over_ranks(el), last
 
     def measure(run_k):
-        """W warm-up steps; ONE drained K-step region (the literal contract); then regions of `reps` back-to-back
-        repetitions of the K-step loop (reps*K blocks issued without draining in between, each region bracketed by
-        barrier + synchronize, max over ranks), enough of them to cover --min-seconds.  The median region gives the
-        steady-state ms_per_step.  Returns (seconds per K steps, [seconds per K steps of every region], last timing
-        object, reps, seconds of the single drained K-step region)."""
-        job = 0
+        """W warm-up steps (blocks 0 .. W-1), then ONE timed region of exactly K steps (blocks W .. W+K-1) bracketed by
+        barrier + synchronize, max over ranks.  Returns (seconds for the K steps, the region's timing object)."""
         if args.warmup:
-            run_k(job, args.warmup); job += args.warmup
-        single, _ = timed(run_k, job, args.steps); job += args.steps
-        # same decisions on every rank: they are made from the reduced time
-        reps = int(min(20000, max(1, np.ceil(0.1 / max(single, 1e-6)))))          # one region ~ 0.1 s
-        nreg = int(min(50, max(5, np.ceil(args.min_seconds / 0.1))))
-        times, last = [], None
-        for _ in range(nreg):
-            el, last = timed(run_k, job, reps * args.steps)
-            times.append(el / reps)
-            job += reps * args.steps
-        return statistics.median(times), times, last, reps, single
+            run_k(0, args.warmup)
+        return timed(run_k, args.warmup, args.steps)
 
     legs = {}
     leg_seconds = {}                      # wall seconds of every leg of this run (rank 0): the time budget of the bench line
     # ---- everything the line is built from exists from here on (None until its leg has run), so that the line can be printed at ANY moment:
     # by the normal end of the run, or by the watchdog when a leg overruns its time budget (round 5: one bench run with every stream
     # CU-masked never came back and cost the whole record -- a hung leg must cost its own numbers, not the line)
-    roof = cpu = crt = crt_shared = dropin = dropin_paced = dropin_sharded = crt_pcie = next_rows = None
+    roof = cpu = crt = crt_shared = dropin = dropin_paced = dropin_sharded = crt_pcie = next_rows = dumped = None
     rccl_ranks, ranks_info, eng_lanes, eng_plan = 0, None, eng.lanes, eng.plan
     main_leg = intended_leg = None
     exchange_errors = {}
@@ -1244,13 +1263,11 @@ def main():
     def emit(leg_timeouts):
         if not emitted.acquire(blocking=False):
             return
-        elapsed, times, timing, reps, single = legs[main_leg] if main_leg in legs else (None, None, None, None, None)
+        elapsed, timing = legs[main_leg] if main_leg in legs else (None, None)
         if rank == 0:
             def leg_obj(name, leg):
-                el, ts, tm, rp, sg = leg
-                return {"ms_per_step": el * 1e3 / args.steps, "value": nch * world * BLOCKTIME / (el / args.steps), "reps": rp, "regions": len(ts),
-                        "ms_per_step_min": min(ts) * 1e3 / args.steps, "ms_per_step_max": max(ts) * 1e3 / args.steps,
-                        "drained_k_step_region_ms_per_step": sg * 1e3 / args.steps,
+                el, tm = leg
+                return {"ms_per_step": el * 1e3 / args.steps, "value": nch * world * BLOCKTIME / (el / args.steps),
                         "gpu_event_ms_per_step": tm.total_ms / tm.blocks, "host_enqueue_ms_per_step": tm.enqueue_ms / tm.blocks}
             have = elapsed is not None
             ms_per_step = elapsed * 1e3 / args.steps if have else None
@@ -1272,19 +1289,16 @@ def main():
                 "metric": "channels sustained @%.1f MS/s input (real-time-equivalent: channel-blocks/s / 50)" % (wl["fs"] / 1e6),
                 "value": value, "unit": "channels", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                 "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                "dtype": "f32", "data": "synthetic",
+                "dtype": "f32", "data": "synthetic", "timed_steps": timing.blocks if have else None,
                 "config": {"workload": wl["name"] + (", 1 MI355X" if world == 1 else ""), "baseline_config": config,
                            "channels_total": total_ch, "P": P, "olen": olen, "N": wl["N"], "L": wl["L"], "M": wl["M"],
                            "launch": ("hipGraph replays of >= %s blocks" % os.environ.get("CHZ_GRAPH_BLOCKS", "32") if graph else "eager") + ", %d HIP streams, notch recurrence ordered by %s"
                                      % (eng_lanes, "HIP events" if os.environ.get("CHZ_NOTCH_ORDER") == "event" else "device ticket"),
                            "plan": eng_plan, "lanes": eng_lanes,
                            "value_is": "free-running channel-blocks/s / 50 of this configuration, inputs resident in HBM; the literal simultaneous-channel count is c_rt.channels"},
-                "timing": "steady state: median over `regions` timed regions, each = `reps` back-to-back repetitions of the K-step loop "
-                          "(reps*K blocks, barrier+sync on both sides, max over ranks); drained_k_step_region = ONE K-step region on its own, "
-                          "pipeline fill and drain included",
-                "reps": reps, "regions": len(times) if have else None, "ms_per_step_min": min(times) * 1e3 / args.steps if have else None,
-                "ms_per_step_max": max(times) * 1e3 / args.steps if have else None,
-                "drained_k_step_region_ms_per_step": single * 1e3 / args.steps if have else None,
+                "timing": "after `warmup` steps, ONE timed region of exactly `steps` steps (barrier+sync on both sides, max over ranks), "
+                          "pipeline fill and drain included; ms_per_step = its time / steps",
+                "dumped_outputs": dumped,
                 "exchange": exchange_desc, "exchange_mode": (main_leg if config == 4 else None),
                 "legs": {k: leg_obj(k, v) for k, v in legs.items() if k != main_leg} or None,
                 "blocks_per_s": args.steps / elapsed if have else None, "realtime_margin": BLOCKTIME / (elapsed / args.steps) if have else None,
@@ -1351,7 +1365,15 @@ def main():
         intended_leg = "replicate" if config == 4 else "local"
         legs[intended_leg] = measure(lambda job0, k: eng.run_blocks(job0, k, graph=graph))
         main_leg = intended_leg
-    elapsed, times, timing, reps, single = legs[main_leg]
+    elapsed, timing = legs[main_leg]
+    if args.dump_outputs:
+        # the timed path's last step (block W+K-1; every leg above ran the same blocks): its spectrum slot and every channel's output,
+        # read before any later leg runs blocks on this engine.  Several ranks: each writes its own channels, rank 0 the spectrum.
+        slot = (args.warmup + args.steps - 1) % 4
+        arrays = {"channels" if world == 1 else "channels_rank%d" % rank: bank.read_slot(slot)}
+        if rank == 0:
+            arrays["spectrum"] = eng.spectrum(slot)
+        dumped = dict(dump_outputs(args.dump_outputs, arrays), job=args.warmup + args.steps - 1, dir=args.dump_outputs)
     leg_seconds["headline_and_exchange_legs"] = time.perf_counter() - t_leg
     t_leg = time.perf_counter()
 

@@ -2,9 +2,9 @@
  *
  * north_star: "drops in behind ka9q-radio's existing filter.h API ... so radiod, linear.c and fm.c are untouched".  This program is the
  * evidence: it is linked from the reference's radio.c, linear.c, fm.c, spectrum.c, modes.c, osc.c, misc.c, iir.c, rtp.c, sched.c, sincospi.c,
- * window.c, compiled UNMODIFIED from where they lie (tests/c/Makefile; never copied), plus this one translation unit, TWICE:
+ * window.c, compiled UNMODIFIED from where they lie (oracle/Makefile; never copied), plus this one translation unit, TWICE:
  *     oracle/_ref/mini_radiod_ref        + the reference's own filter.c on the oracle's FFT provider  (the checker)
- *     tests/c/_prebuilt/mini_radiod_hip  + libka9q_filter_hip.so                                      (the product under test)
+ *     oracle/_ref/mini_radiod_hip        + libka9q_filter_hip.so                                      (the product under test)
  * Everything between the A/D samples and the PCM frames is the reference's code: lookup_or_create_chan() / start_demod() /
  * demod_thread() (src/radio.c:862-998), one pthread per channel in demod_linear() (src/linear.c:21-375) or demod_fm()
  * (src/fm.c:19-345), each calling downconvert() (src/radio.c:1410-1524): compute_tuning, execute_filter_output (:1460),

@@ -12,7 +12,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_EXE = os.path.join(ROOT, "oracle", "_ref", "mini_radiod_ref")           # the reference's filter.c (checker)
-HIP_EXE = os.path.join(ROOT, "tests", "c", "_prebuilt", "mini_radiod_hip")  # libka9q_filter_hip.so (product)
+HIP_EXE = os.path.join(ROOT, "oracle", "_ref", "mini_radiod_hip")           # libka9q_filter_hip.so (product)
+CALLER_OBJS = os.path.join(ROOT, "oracle", "_ref", "mini_radiod")           # the caller objects both are linked from (oracle/Makefile)
 
 # /root/reference/share/presets.conf, the sections this test uses (line numbers of the section headers)
 PRESETS = {

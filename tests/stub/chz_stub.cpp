@@ -5,6 +5,7 @@
 // every engine entry point the drop-in calls is an operation on ONE in-order work queue served by a worker thread, so that, as on the
 // device, calls return before their work is done and the completion callback runs on a thread that is not the caller's.
 // Never built into, linked with or loaded by the product (tests/test_dropin_stub.py builds it into tests/stub/_build/).
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <complex>
@@ -49,6 +50,7 @@ struct chz_engine {
   std::atomic<int> nbanks{0};
   std::thread worker; std::mutex m; std::condition_variable cv, idle;
   std::atomic<bool> failed{false}; int fail_job = -1;     // fault injection (CHZ_STUB_FAIL_JOB)
+  std::mutex fm; std::condition_variable fcv; long long handed = -1;     // the last block handed over (CHZ_STUB_FAIL_HOLD)
   std::mutex mm; std::condition_variable mcv; unsigned long long mark_seq = 0, mark_want[8] = {}, mark_done[8] = {};   // chz_input_mark
   std::deque<std::function<void()>> q; bool busy = false, quit = false;
   void post(std::function<void()> f) { { std::lock_guard<std::mutex> lk(m); q.push_back(std::move(f)); } cv.notify_one(); }
@@ -148,7 +150,17 @@ int chz_input_write(chz_engine* e, const float* x, long n) {
 }
 int chz_forward(chz_engine* e, unsigned job) {
   if (!e) return fail(-1, "null engine");
-  if (e->fail_job >= 0 && (int)job >= e->fail_job) e->post([e] { e->failed.store(true, std::memory_order_release); });
+  static const bool hold = [] { const char* v = getenv("CHZ_STUB_FAIL_HOLD"); return v && v[0] == '1'; }();
+  if (hold) { { std::lock_guard<std::mutex> lk(e->fm); e->handed = std::max(e->handed, (long long)job); } e->fcv.notify_all(); }
+  if (e->fail_job >= 0 && (int)job >= e->fail_job) e->post([e, job] {
+    // CHZ_STUB_FAIL_HOLD=1: the failure of block n shows only once block n+1 has been handed over too (at most 2 s), so that the check fails with two blocks in
+    // flight whatever the host's scheduling -- as a device that is still busy with n when its successor is enqueued
+    if (hold && (int)job == e->fail_job) {
+      std::unique_lock<std::mutex> lk(e->fm);
+      e->fcv.wait_for(lk, std::chrono::seconds(2), [&] { return e->handed > (long long)job; });
+    }
+    e->failed.store(true, std::memory_order_release);
+  });
   e->post([e, job] {
     // CHZ_STUB_WEDGE_JOB=n: from block n on the device neither completes anything nor reports anything (a wedged device)
     static const int wedge = [] { const char* v = getenv("CHZ_STUB_WEDGE_JOB"); return v ? atoi(v) : -1; }();

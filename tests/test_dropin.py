@@ -23,7 +23,10 @@ PKG = os.path.join(ROOT, "ka9q-radio_amd")
 # tests/test_engine_emulated.py re-runs the harness tests against the drop-in linked with the CPU build of the engine: the two
 # libraries are then taken from this directory instead (and not rebuilt by `make`)
 LIBDIR = os.environ.get("KA9Q_TEST_LIBDIR", PKG)
-REF_SRC = "/root/reference/src"
+# the harness compiled against the reference's OWN src/filter.h, and that object linked on the drop-in: built by oracle/Makefile (__graft_entry__.build(),
+# where the reference tree exists) -- kept in oracle/_ref/ with the other reference builds, so that the GPU tier can RUN a caller that has never seen include/ka9q_filter_abi.h
+REF_HARNESS_OBJ = os.path.join(ROOT, "oracle", "_ref", "harness_refhdr.o")
+PREBUILT_REF_HARNESS = os.path.join(ROOT, "oracle", "_ref", "harness_refhdr")
 
 
 def _build_lib():
@@ -32,13 +35,9 @@ def _build_lib():
 
 
 def _build_harness(out, ref_header=False):
-    cmd = ["gcc", "-O2", "-std=gnu11", "-Wall", os.path.join(ROOT, "tests", "c", "dropin_harness.c"), "-o", out,
-           "-L", LIBDIR, "-lka9q_filter_hip", "-lchz_hip", "-Wl,-rpath," + LIBDIR, "-lpthread", "-lm"]
-    if ref_header:
-        cmd[4:4] = ["-DKA9Q_FILTER_HEADER=\"filter.h\"", "-DHARNESS_REF_HEADER=1", "-D_GNU_SOURCE=1", "-I", os.path.join(ROOT, "oracle", "shims"), "-iquote", REF_SRC]
-    else:
-        cmd[4:4] = ["-I", os.path.join(ROOT, "include")]
-    subprocess.run(cmd, check=True)
+    """ref_header=True: link the caller object compiled against the reference's own filter.h (oracle/_ref/harness_refhdr.o) instead"""
+    src = [REF_HARNESS_OBJ] if ref_header else ["-std=gnu11", "-Wall", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "c", "dropin_harness.c")]
+    subprocess.run(["gcc", "-O2"] + src + ["-o", out, "-L", LIBDIR, "-lka9q_filter_hip", "-lchz_hip", "-Wl,-rpath," + LIBDIR, "-lpthread", "-lm"], check=True)
 
 
 def test_dropin_exports_the_reference_symbol_set():
@@ -64,7 +63,7 @@ def test_dropin_exports_the_reference_symbol_set():
         assert ref_syms <= mine, ref_syms - mine
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="/root/reference absent")
+@pytest.mark.skipif(not os.path.exists(REF_HARNESS_OBJ), reason="oracle/_ref/harness_refhdr.o not built (needs the reference tree at build time)")
 def test_caller_compiled_against_reference_header_links(tmp_path):
     _build_lib()
     _build_harness(str(tmp_path / "h_ref"), ref_header=True)
@@ -156,30 +155,14 @@ def test_dropin_master_and_slave_lengths_fftw_would_plan():
     _check(L, M, olen, P, plan, nblocks, out, spec, meta, x)
 
 
-PREBUILT_REF_HARNESS = os.path.join(ROOT, "tests", "c", "_prebuilt", "harness_refhdr")
-
-
-def build_ref_header_harness():
-    """The harness compiled against the reference's OWN src/filter.h, where /root/reference exists (this container): the binary
-    travels to the GPU box with the snapshot (it is git-ignored, like the other built artefacts), so that the GPU tier can RUN a
-    caller that has never seen include/ka9q_filter_abi.h.  Called by __graft_entry__.build()."""
-    if not os.path.isdir(REF_SRC) or LIBDIR != PKG:
-        return None
-    os.makedirs(os.path.dirname(PREBUILT_REF_HARNESS), exist_ok=True)
-    _build_harness(PREBUILT_REF_HARNESS, ref_header=True)
-    return PREBUILT_REF_HARNESS
-
-
 @pytest.mark.gpu
 def test_dropin_runs_a_caller_built_against_the_reference_header():
     """round 2 only LINKED such a caller; here it runs on the device: struct layouts, enum values and every function signature are
     the reference's own (src/filter.h:29-118), the library underneath is the drop-in."""
     _build_lib(); ol.build()
     exe = PREBUILT_REF_HARNESS
-    if os.path.isdir(REF_SRC):
-        build_ref_header_harness()
     if not os.path.exists(exe):
-        pytest.fail("tests/c/_prebuilt/harness_refhdr is missing: __graft_entry__.build() makes it where /root/reference exists")
+        pytest.fail("oracle/_ref/harness_refhdr is missing: __graft_entry__.build() makes it where the reference tree exists")
     L, M, olen, P = 25920, 6481, 240, 300
     nblocks = 7
     rng = np.random.default_rng(9)
@@ -211,10 +194,8 @@ def test_dropin_packetd_style_analytic_filter():
     masters.  The caller is compiled against the reference's OWN filter.h."""
     _build_lib(); ol.build()
     exe = PREBUILT_REF_HARNESS
-    if os.path.isdir(REF_SRC):
-        build_ref_header_harness()
     if not os.path.exists(exe):
-        pytest.fail("tests/c/_prebuilt/harness_refhdr is missing: __graft_entry__.build() makes it where /root/reference exists")
+        pytest.fail("oracle/_ref/harness_refhdr is missing: __graft_entry__.build() makes it where the reference tree exists")
     L, M, olen = 960, 961, 960
     N = L + M - 1
     nblocks = 12

@@ -2,10 +2,10 @@
 compiled unmodified from /root/reference/src -- running on the drop-in, A/B against the same objects on the reference's filter.c.
 
 north_star: "drops in behind ka9q-radio's existing filter.h API ... so radiod, linear.c and fm.c are untouched".  tests/c/mini_radiod.c
-says what is the reference's and what is stubbed; tests/c/Makefile links it twice from ONE set of caller objects:
+says what is the reference's and what is stubbed; oracle/Makefile links it twice from ONE set of caller objects (oracle/_ref/mini_radiod/):
     oracle/_ref/mini_radiod_ref        + the reference's filter.c (+ the oracle's float64 FFT provider)     -- the checker
-    tests/c/_prebuilt/mini_radiod_hip  + libka9q_filter_hip.so -> libchz_hip.so (the hand-written kernels)  -- the product
-Both are built by __graft_entry__.build() where /root/reference exists and travel to the GPU box.
+    oracle/_ref/mini_radiod_hip        + libka9q_filter_hip.so -> libchz_hip.so (the hand-written kernels)  -- the product
+All three are built by __graft_entry__.build() where the reference tree exists; the GPU tier runs them from oracle/_ref/.
 
 CPU tier: the checker link runs and the channel table does what it is meant to (squelch closed on empty channels, PL tone found, PLL
 locks, filter2 = 4 decimates the frame rate, commands land); the SAME callers on the drop-in's host code over the CPU stand-in engine
@@ -14,6 +14,7 @@ GPU tier: the product link on the MI355X against the checker link, the bar of th
 frame kinds / mute flags / squelch / timestamps / bin shifts / block_drops identical, float PCM <= 1e-5 rel-L2, int16 PCM <= 1 LSB on
 <= 0.1 % of the samples, sig.n0 and bb_power within 1e-5."""
 import os
+import re
 import subprocess
 import tempfile
 
@@ -24,10 +25,10 @@ import mini_radiod_lib as mr
 import oracle_lib as ol
 
 ROOT = mr.ROOT
-REF_SRC = "/root/reference/src"
 FS, L, M, NBLOCKS = 1.296e6, 25920, 6481, 30        # N = 32,400: 40 Hz bins, 20 ms blocks, overlap 5
 
-needs_ref_exe = pytest.mark.skipif(not os.path.exists(mr.REF_EXE), reason="oracle/_ref/mini_radiod_ref not built (needs /root/reference at build time)")
+needs_ref_exe = pytest.mark.skipif(not os.path.exists(mr.REF_EXE), reason="oracle/_ref/mini_radiod_ref not built (needs the reference tree at build time)")
+needs_caller_objs = pytest.mark.skipif(not os.path.isdir(mr.CALLER_OBJS), reason="oracle/_ref/mini_radiod/ not built (needs the reference tree at build time): no caller objects to link")
 
 
 def _kinds(frames):
@@ -113,12 +114,13 @@ def _build_stub_link(out_dir, sanitize=None):
     subprocess.run(["gcc", "-g", "-std=gnu11", "-fPIC", "-shared"] + san + [os.path.join(ROOT, "ka9q-radio_amd", "csrc", "filter_hip.c"), "-o",
                     os.path.join(out_dir, "libka9q_filter_hip.so"), "-L", out_dir, "-lchz_hip", "-Wl,-rpath,$ORIGIN", "-lm", "-lpthread"], check=True)
     exe = os.path.join(out_dir, "mini_radiod_stub")
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "c"), "LIBDIR=" + out_dir, "OUT_HIP=" + exe, exe] + (["LINK_EXTRA=-fsanitize=" + sanitize] if sanitize else []), check=True)
+    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "LIBDIR=" + out_dir, "MR_OUT=" + exe, "MR_RPATH=" + out_dir, "mini-radiod-link"]
+                   + (["LINK_EXTRA=-fsanitize=" + sanitize] if sanitize else []), check=True)
     return exe
 
 
 @needs_ref_exe
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="/root/reference absent: the caller objects cannot be linked here")
+@needs_caller_objs
 def test_reference_callers_on_the_dropin_host_code_over_the_cpu_stand_in(tmp_path):
     exe = _build_stub_link(str(tmp_path))
     ch = mr.standard_channels()
@@ -135,7 +137,7 @@ CONFIG2 = (64.8e6, 1296000, 324001)      # BASELINE config 2: N = 1,620,000, 256
 
 
 @needs_ref_exe
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="/root/reference absent: the caller objects cannot be linked here")
+@needs_caller_objs
 def test_config3_through_the_reference_callers_on_the_dropin_host_code(tmp_path):
     """BASELINE config 3 itself -- 129.6 MS/s real, 1024 mixed usb / cw / iq channels, one REAL radiod channel thread each (demod_thread ->
     demod_linear -> downconvert; the CW third with filter2 = 4: 341 pooled inline masters) -- on the drop-in's host code over the CPU
@@ -154,7 +156,7 @@ def test_config3_through_the_reference_callers_on_the_dropin_host_code(tmp_path)
 
 
 @needs_ref_exe
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="/root/reference absent: the caller objects cannot be linked here")
+@needs_caller_objs
 def test_complex_front_end_and_sharded_master_on_the_dropin_host_code(tmp_path):
     """the two remaining shapes of BASELINE.json through the reference's callers on the drop-in's host code (stand-in engine): config 1 -- a
     COMPLEX 2.4 MS/s front end (write_cfilter), one IQ channel and one at a negative frequency --, and config 4's shape -- 2000 x 24 kHz
@@ -190,7 +192,7 @@ def _check_churn(fr, nblocks):
 
 
 @needs_ref_exe
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="/root/reference absent: the caller objects cannot be linked here")
+@needs_caller_objs
 def test_channels_joining_and_leaving_on_the_dropin_host_code(tmp_path):
     """radiod's dynamic channels through the reference's own lifecycle code on the drop-in's host code (stand-in engine): eight channels run
     out of lifetime mid-stream (close_chan -> delete_filter_output while 50 others run), ten join mid-stream (create_filter_output on a
@@ -218,7 +220,7 @@ def _check_spectrum(fr, wide, nblocks):
 
 
 @needs_ref_exe
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="/root/reference absent: the caller objects cannot be linked here")
+@needs_caller_objs
 def test_spectrum_analysers_on_the_dropin_host_code(tmp_path):
     """src/spectrum.c's demod_spectrum() on the drop-in's host code (stand-in engine): three narrowband analysers -- COMPLEX slaves of 208, 520 and
     60 samples per block, sizes no demodulator asks for; set_filter() with a Kaiser beta of its own; the analysis transform planned through
@@ -253,7 +255,7 @@ def _check_wfm(fr, nblocks):
 
 
 @needs_ref_exe
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="/root/reference absent: the caller objects cannot be linked here")
+@needs_caller_objs
 def test_wfm_stereo_decoder_on_the_dropin_host_code(tmp_path):
     """src/wfm.c's demod_wfm() on the drop-in's host code (stand-in engine): a 384 kHz COMPLEX slave off the front end (7680 samples per block, P = 9600),
     and -- per channel -- a REAL inline master of its own (the FM composite: L = 7680, M = 7681, N = 15,360, perform_inline set AFTER creation) with a
@@ -270,14 +272,16 @@ def test_wfm_stereo_decoder_on_the_dropin_host_code(tmp_path):
     # with the master's slaves spread over two (stand-in) devices: the front-end master is, the WFM channels' private composite masters (15,360 points, three
     # slaves each) are not -- every listed device would copy and transform their every block for nothing (filter_hip.c: SHARD_MIN_POINTS)
     B, meta, err = mr.run(exe, str(tmp_path / "got2"), ch, x, fs, l, m, NBLOCKS, env={"CHZ_STUB_DEVICES": "2", "KA9Q_HIP_DEVICES": "0,1", "KA9Q_HIP_PROFILE": "1"})
-    prof = [dict(t.split("=") for t in ln.split() if "=" in t) for ln in err.splitlines() if ln.startswith("filter_hip profile:")]
+    # (one profile record per master, each printed by one fprintf; the masters are deleted by their own threads, so a record may land in the middle of
+    # another master's multi-part "first blocks" line: it runs from its tag to the end of that line)
+    prof = [dict(t.split("=") for t in rec.split() if "=" in t) for rec in re.findall(r"filter_hip profile: (.*)", err)]
     assert sorted((int(p["points"]), int(p["devices"])) for p in prof) == [(15360, 1)] * 3 + [(64800, 2)], prof     # (the empty WFM channel never opens its squelch: its composite master never runs a block and prints nothing)
     s = mr.check(mr.diff(A, B, settle=WFM_SETTLE), None, float_tol=1e-6, n0_tol=1e-9)
     assert s["frames_in_agreement"] == s["frames"], s
 
 
 @needs_ref_exe
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="/root/reference absent: the caller objects cannot be linked here")
+@needs_caller_objs
 def test_wfm_deletes_its_master_before_its_slaves_without_leaks(tmp_path):
     """src/wfm.c:290-293 ends with delete_filter_input(&composite) FIRST and the three delete_filter_output() after it; the reference's
     delete_filter_output never looks at the master (src/filter.c:943-957).  The drop-in's host code under AddressSanitizer + LeakSanitizer through the whole
@@ -301,7 +305,7 @@ def test_wfm_deletes_its_master_before_its_slaves_without_leaks(tmp_path):
 
 
 @needs_ref_exe
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="/root/reference absent: the caller objects cannot be linked here")
+@needs_caller_objs
 def test_reference_callers_on_the_dropin_host_code_under_thread_sanitizer(tmp_path):
     """the drop-in's host code and the stand-in engine compiled with -fsanitize=thread under the reference's own threads (pthread calls of the
     uninstrumented caller objects are intercepted all the same): channels joining and leaving a running master, and WFM channels creating and
@@ -321,7 +325,7 @@ def test_reference_callers_on_the_dropin_host_code_under_thread_sanitizer(tmp_pa
 
 
 @needs_ref_exe
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="/root/reference absent: the caller objects cannot be linked here")
+@needs_caller_objs
 def test_small_complex_front_end_on_the_dropin_host_code(tmp_path):
     """a Funcube dongle's front end (192 kHz COMPLEX, N = 4800) under the reference's callers on the drop-in's host code: to create_filter_input such a master
     looks like radiod's filter2; the first channel's decimating slave turns it into an engine in place, while the CW channel's filter2 = 4 next to it IS a
@@ -350,7 +354,7 @@ def _check_switches(fr, nblocks):
 
 
 @needs_ref_exe
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="/root/reference absent: the caller objects cannot be linked here")
+@needs_caller_objs
 def test_presets_and_sample_rates_changed_on_running_channels_on_the_dropin_host_code(tmp_path):
     """what `control` does to a running channel, through the reference's own restart path (src/radio_status.c:613-660 -> src/radio.c:940-985): a new sample rate
     or demodulator makes the channel thread delete its filter output and create one of another size on the running master; a CW preset on a running USB
@@ -366,7 +370,7 @@ def test_presets_and_sample_rates_changed_on_running_channels_on_the_dropin_host
 
 
 @needs_ref_exe
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="/root/reference absent: the caller objects cannot be linked here")
+@needs_caller_objs
 def test_a_leaving_beam_channel_does_not_hand_its_beam_form_to_the_slave_that_takes_its_index(tmp_path):
     """round 6, found by running the reference's callers: when a slave in beam mode (src/radio.c:938-940) was deleted, the slave that took over its bank index was
     computed with the leaver's beam weights from then on -- the host's record of what is uploaded at that index was stale"""
@@ -383,7 +387,7 @@ def test_a_leaving_beam_channel_does_not_hand_its_beam_form_to_the_slave_that_ta
 
 
 @needs_ref_exe
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="/root/reference absent: the caller objects cannot be linked here")
+@needs_caller_objs
 def test_a_device_failure_under_the_reference_callers(tmp_path):
     """the stand-in engine reports a failed device-side check at block 10 (CHZ_STUB_FAIL_JOB) while 48 channel threads of the reference's own code run: the drop-in
     replaces its engine, the blocks in flight are counted drops (zeros, src/filter.c:690-701), every thread keeps its frame count and carries on -- no hang,
@@ -392,7 +396,7 @@ def test_a_device_failure_under_the_reference_callers(tmp_path):
     ch = mr.standard_channels()
     x = mr.synthesise(ch, FS, L, NBLOCKS)
     A, _, _ = _reference_run(str(tmp_path), ch, x)
-    B, meta, err = mr.run(exe, str(tmp_path / "got"), ch, x, FS, L, M, NBLOCKS, env={"CHZ_STUB_FAIL_JOB": "10"}, timeout=300)
+    B, meta, err = mr.run(exe, str(tmp_path / "got"), ch, x, FS, L, M, NBLOCKS, env={"CHZ_STUB_FAIL_JOB": "10", "CHZ_STUB_FAIL_HOLD": "1"}, timeout=300)
     assert "re-creating the engine" in err and int(meta["shutdowns"]) == 1
     assert sorted(B) == sorted(A) and all(len(B[k]) == len(A[k]) for k in A)
     drops = {F[-1]["block_drops"] for F in B.values()}
@@ -403,7 +407,7 @@ def test_a_device_failure_under_the_reference_callers(tmp_path):
 
 
 @needs_ref_exe
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="/root/reference absent: the caller objects cannot be linked here")
+@needs_caller_objs
 @pytest.mark.parametrize("env", [{"CHZ_STUB_DEVICES": "2", "KA9Q_HIP_DEVICES": "0,1", "KA9Q_HIP_SHARD_CHANNELS": "7"},
                                  {"CHZ_STUB_DEVICES": "3", "KA9Q_HIP_DEVICES": "0,1,2", "KA9Q_HIP_SHARD_CHANNELS": "5", "KA9Q_HIP_EXCHANGE": "broadcast"}], ids=["two_devices_samples", "three_devices_broadcast"])
 def test_sharded_master_under_the_reference_callers(tmp_path, env):
@@ -420,9 +424,7 @@ def test_sharded_master_under_the_reference_callers(tmp_path, env):
 
 
 def _hip_exe():
-    if os.path.isdir(REF_SRC):          # (this container: rebuild if the sources or the libraries changed; the GPU box runs what travelled)
-        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "c"), "all"], check=True)
-    assert os.path.exists(mr.HIP_EXE), "tests/c/_prebuilt/mini_radiod_hip missing: __graft_entry__.build() makes it where /root/reference exists"
+    assert os.path.exists(mr.HIP_EXE), "oracle/_ref/mini_radiod_hip missing: __graft_entry__.build() makes it where the reference tree exists"
     assert os.path.exists(mr.REF_EXE), "oracle/_ref/mini_radiod_ref missing"
     return mr.HIP_EXE
 
