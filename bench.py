@@ -19,6 +19,12 @@ Timing: after W warm-up steps, ONE region of exactly K = --steps steps is timed 
 (barrier across ranks on both sides, max over ranks): ms_per_step = its time / K, pipeline fill and drain included
 (a K of a few seconds' worth of steps amortises them).
 
+A plain run does only what the headline needs: set-up, the W warm-up and K timed steps, the dump (--dump-outputs), the
+line.  At --gpus > 1 it also times the replicate leg first (the line's fall-back if an exchange fails or hangs) and stops
+at the first exchange that works.  --full adds everything else, each leg as before: the roofline (per-kernel times,
+pipelined and streamed forward transform), C_rt, the CPU baseline, the filter.h drop-in legs, C_rt over PCIe, the
+SURVEY 8f chain and, at --gpus > 1, every exchange leg.  --quick is a --full run cut down to the roofline.
+
 --dump-outputs DIR: after the timed steps, what the timed path computed in its LAST step -- the block's spectrum and
 every channel's output, as a caller receives them -- goes to DIR/<name>.npy in float32 (complex as a trailing
 re/im axis; at most 64 MB in all, larger arrays as a fixed seeded sample of their rows).  The inputs depend on the
@@ -1022,7 +1028,7 @@ def headline(out, detail_path):
                                           **{k: (x.get("paced") or {}).get(k) for k in ("drops_first_8_blocks", "block0_ms", "p99_ms", "max_ms")}))
     many("c_rt_pcie", lambda x: _pick(x, "channels", "sustained", "worst_block_ms", "d2h_bytes_per_channel", "pcm_mismatches"))
     many("next_rows", lambda x: dict(_pick(x, "mode", "channels", "pcm_mismatches", "verified_channels"), ms_per_block=x.get("pipelined_ms_per_block")))
-    h.update(_pick(out, "leg_seconds", "rccl_ranks", "quick", "leg_timeouts", "headline_from", "exchange_errors"))
+    h.update(_pick(out, "leg_seconds", "rccl_ranks", "quick", "full", "leg_timeouts", "headline_from", "exchange_errors"))
     h["detail"] = detail_path
     h = _clean(h, 5)
     line = json.dumps(h, allow_nan=False, separators=(",", ":"))
@@ -1064,6 +1070,9 @@ def main():
     ap.add_argument("--min-seconds", type=float, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="write the spectrum and the channel outputs of the last timed step to DIR/<name>.npy (float32, <= 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg too (roofline, C_rt, CPU baseline, drop-in, PCIe, 8f chain, every exchange); "
+                         "the --no-* and leg-size options below shape such a run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--graph", action="store_true", help="replay one hipGraph per ring cycle instead of eager launches (N=1)")
     ap.add_argument("--no-crt", action="store_true", help="skip the C_rt leg (one large bank, every block inside 20 ms)")
@@ -1083,13 +1092,20 @@ def main():
     ap.add_argument("--detail", default=os.environ.get("BENCH_DETAIL", ""), help="where the full detail object goes (default gpurun_out/bench_detail.json); "
                     "stdout's last line is the compact headline (< 6 KB)")
     ap.add_argument("--quick", action="store_true",
-                    help="iteration mode: the headline and the roofline object only (no C_rt ladder, PCIe probes, 8f chain, drop-in or CPU legs): "
-                         "< 30 s of GPU time.  The driver's command (no --quick) keeps the full line")
+                    help="iteration mode: --full cut down to the roofline object (no C_rt ladder, PCIe probes, 8f chain, drop-in or CPU legs): "
+                         "< 30 s of GPU time")
     args = ap.parse_args()
     if args.min_seconds is not None:
         print("bench.py: --min-seconds is ignored: the timed region is exactly --steps steps", file=sys.stderr)
     if args.quick:
+        args.full = True
         args.no_crt = args.no_next_rows = args.no_dropin = args.no_dropin_paced = args.no_crt_pcie = args.no_cpu_baseline = True
+    if not args.full:
+        shaping = ("no_cpu_baseline", "no_crt", "crt_channels", "crt_blocks", "no_next_rows", "next_rows_channels", "next_rows_modes", "crt_ladder",
+                   "no_dropin", "dropin_blocks", "no_dropin_paced", "no_crt_pcie", "crt_pcie_blocks", "crt_shared")
+        given = ["--" + k.replace("_", "-") for k in shaping if getattr(args, k) != ap.get_default(k)]
+        if given:
+            print("bench.py: %s shape the legs of a --full run: this plain run ignores them" % ", ".join(given), file=sys.stderr)
     if args.gpus < 1 or args.steps < 1 or args.warmup < 0:
         raise SystemExit("bad --gpus/--steps/--warmup")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1312,7 +1328,7 @@ def main():
                 "roofline": roof, "cpu_baseline": cpu, "c_rt": crt, "c_rt_shared_responses": crt_shared,
                 "dropin": dropin, "dropin_paced": dropin_paced, "dropin_sharded": dropin_sharded, "c_rt_pcie": crt_pcie, "next_rows": next_rows,
                 "leg_seconds": {k: round(v, 1) for k, v in leg_seconds.items()},
-                "rccl_ranks": rccl_ranks, "ranks": ranks_info, "quick": bool(args.quick),
+                "rccl_ranks": rccl_ranks, "ranks": ranks_info, "quick": bool(args.quick), "full": bool(args.full),
             }
         if rank == 0:
             # RCCL prints a banner through C stdio: flush it first so the JSON is the LAST line of stdout
@@ -1354,6 +1370,8 @@ def main():
         if not (world > 1 or os.environ.get("BENCH_ALL_EXCHANGES") == "1"):
             ladder = ladder[:1]
         for m in ladder:
+            if main_leg != "replicate" and not args.full:
+                break                                                # a plain run needs the first hand-over that works, no more
             progress("exchange " + m)
             try:
                 legs[m] = measure(run_sharded(m))
@@ -1375,8 +1393,32 @@ def main():
             arrays["spectrum"] = eng.spectrum(slot)
         dumped = dict(dump_outputs(args.dump_outputs, arrays), job=args.warmup + args.steps - 1, dir=args.dump_outputs)
     leg_seconds["headline_and_exchange_legs"] = time.perf_counter() - t_leg
-    t_leg = time.perf_counter()
 
+    def close_engine():
+        nonlocal rccl_ranks, eng_lanes, eng_plan, ranks_info
+        rccl_ranks = comm.world if comm is not None else 0
+        if comm is not None:
+            comm.close()
+        eng_lanes, eng_plan = eng.lanes, eng.plan
+        eng.close()
+        ranks_info = [{"rank": rank, "device": dev_index, "device_name": torch.cuda.get_device_name(dev_index)}]
+        if use_dist:
+            allr = [None] * world
+            dist.all_gather_object(allr, ranks_info[0])
+            ranks_info = allr
+
+    def finish():
+        wd["leg"] = None                          # nothing left to watch
+        if use_dist:
+            dist.destroy_process_group()
+        emit(())
+
+    if not args.full:
+        close_engine()
+        finish()
+        return
+
+    t_leg = time.perf_counter()
     progress("roofline: per-kernel times")
     # ---- per-kernel durations with HIP events on the launch stream (eager, instrumented; >= 200 launches whatever K is)
     roof = None
@@ -1522,16 +1564,7 @@ def main():
         cpu = cpu_baseline(oracle_lib, ring_host, wl, crt_blocks=args.crt_blocks)
         leg_seconds["cpu_baseline"] = time.perf_counter() - t_leg
 
-    rccl_ranks = comm.world if comm is not None else 0
-    if comm is not None:
-        comm.close()
-    eng_lanes, eng_plan = eng.lanes, eng.plan
-    eng.close()
-    ranks_info = [{"rank": rank, "device": dev_index, "device_name": torch.cuda.get_device_name(dev_index)}]
-    if use_dist:
-        allr = [None] * world
-        dist.all_gather_object(allr, ranks_info[0])
-        ranks_info = allr
+    close_engine()
 
     progress("dropin (free-running)")
     # ---- the boundary itself: the same workload through filter.h (C harness, one pthread per channel), PCIe in the loop
@@ -1626,10 +1659,7 @@ def main():
             except Exception as ex:
                 next_rows.append({"mode": mode, "error": str(ex)[:600]})
         leg_seconds["next_rows"] = time.perf_counter() - t_leg
-    wd["leg"] = None                          # nothing left to watch
-    if use_dist:
-        dist.destroy_process_group()
-    emit(())
+    finish()
 
 
 if __name__ == "__main__":

@@ -30,14 +30,14 @@ tail -$N $P/r06_multigpu_rccl_sanity.txt 2>/dev/null
 step "2: config 5, replicas only, N = 1 2 4 $N"
 for n in 1 2 4 $N; do
   [ $n -gt $N ] && continue
-  timeout 900 python bench.py --gpus $n --config 5 --steps 200 --warmup 50 --detail $P/r06_multigpu_config5_n$n.detail.json > $P/r06_multigpu_config5_n$n.json 2> $P/r06_multigpu_config5_n$n.err
+  timeout 900 python bench.py --full --gpus $n --config 5 --steps 200 --warmup 50 --detail $P/r06_multigpu_config5_n$n.detail.json > $P/r06_multigpu_config5_n$n.json 2> $P/r06_multigpu_config5_n$n.err
   echo "config5 n=$n rc=$? $(tail -c 400 $P/r06_multigpu_config5_n$n.json | head -c 400)"
 done
 
 step "3: config 4 (the metric), every exchange leg, N = 2 4 $N"
 for n in 2 4 $N; do
   [ $n -gt $N ] && continue
-  timeout 1200 python bench.py --gpus $n --steps 200 --warmup 50 --detail $P/r06_multigpu_config4_n$n.detail.json > $P/r06_multigpu_config4_n$n.json 2> $P/r06_multigpu_config4_n$n.err
+  timeout 1200 python bench.py --full --gpus $n --steps 200 --warmup 50 --detail $P/r06_multigpu_config4_n$n.detail.json > $P/r06_multigpu_config4_n$n.json 2> $P/r06_multigpu_config4_n$n.err
   rc=$?
   echo "config4 n=$n rc=$rc"; python - $P/r06_multigpu_config4_n$n.json <<'PY'
 import json, sys
@@ -49,7 +49,7 @@ except Exception as ex:
 PY
   if grep -q '"leg_timeouts":\[' $P/r06_multigpu_config4_n$n.json 2>/dev/null; then
     step "4: config 4 again at n=$n with the notch ordered by HIP events"
-    CHZ_NOTCH_ORDER=event timeout 1200 python bench.py --gpus $n --steps 200 --warmup 50 --detail $P/r06_multigpu_config4_event_n$n.detail.json > $P/r06_multigpu_config4_event_n$n.json 2> $P/r06_multigpu_config4_event_n$n.err
+    CHZ_NOTCH_ORDER=event timeout 1200 python bench.py --full --gpus $n --steps 200 --warmup 50 --detail $P/r06_multigpu_config4_event_n$n.detail.json > $P/r06_multigpu_config4_event_n$n.json 2> $P/r06_multigpu_config4_event_n$n.err
     echo "config4 (event) n=$n rc=$?"
   fi
 done

@@ -7,7 +7,7 @@ name=${1:-tests}
 out=gpurun_out/$name
 mkdir -p "$out"
 export TMPDIR=/tmp
-B="python bench.py --steps 20 --warmup 5"
+B="python bench.py --full --steps 20 --warmup 5"
 case "$name" in
   r6y)       # round 6: the driver's bench command alone (the committed record: profiles re-collected on the final kernel sources first)
     timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.txt" 2>&1; tail -1 "$out/smoke.txt"

@@ -64,7 +64,7 @@ def test_headline_of_the_committed_full_run_is_compact_and_strict():
 
 @pytest.mark.gpu
 def test_bench_emits_one_json_line_with_the_contract_keys(tmp_path):
-    h, j = _run_bench(["--gpus", "1", "--steps", "64", "--warmup", "8", "--crt-channels", "3000000", "--crt-blocks", "40", "--dropin-blocks", "60",
+    h, j = _run_bench(["--full", "--gpus", "1", "--steps", "64", "--warmup", "8", "--crt-channels", "3000000", "--crt-blocks", "40", "--dropin-blocks", "60",
                        "--crt-pcie-blocks", "30", "--next-rows-channels", "300000"], tmp_path)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
@@ -143,7 +143,7 @@ def test_bench_emits_one_json_line_with_the_contract_keys(tmp_path):
 def test_bench_crt_search_reports_a_sustained_count_and_the_mean_crossing(tmp_path):
     """the default C_rt search (no explicit ladder), with short rungs: a sustained count whatever the box, every block of it inside 20 ms,
     the count at which the MEAN block time crosses 20 ms beside it, and never more rungs than the search allows"""
-    h, j = _run_bench(["--steps", "20", "--warmup", "5", "--crt-blocks", "60", "--no-next-rows", "--no-dropin", "--no-dropin-paced", "--no-crt-pcie",
+    h, j = _run_bench(["--full", "--steps", "20", "--warmup", "5", "--crt-blocks", "60", "--no-next-rows", "--no-dropin", "--no-dropin-paced", "--no-crt-pcie",
                        "--no-cpu-baseline"], tmp_path)
     c = j["c_rt"]
     assert c["sustained"] is True and 10_000_000 < c["channels"] <= 22_001_024 and c["worst_block_ms"] <= 20.0 and c["verified_channels"] >= 64
@@ -161,6 +161,32 @@ def test_bench_quick_mode_is_the_headline_only(tmp_path):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_only(tmp_path):
+    """without --full: set-up, warm-up, the timed steps and the line -- no other leg runs, and the process spends little beyond its
+    steps (the other legs take minutes)"""
+    import time
+    t0 = time.perf_counter()
+    h, j = _run_bench(["--gpus", "1", "--steps", "200", "--warmup", "50"], tmp_path, timeout=300)
+    wall = time.perf_counter() - t0
+    assert h["full"] is False and h["quick"] is False and h["steps"] == 200 and h["warmup"] == 50 and j["timed_steps"] == 200
+    assert h["config"]["baseline_config"] == 3 and h["value"] > 0 and abs(j["value"] - 1024 * 0.02 / (j["ms_per_step"] * 1e-3)) <= 1e-6 * j["value"]
+    for k in ("roofline", "cpu_baseline", "c_rt", "dropin", "dropin_paced", "dropin_sharded", "c_rt_pcie", "next_rows"):
+        assert h[k] is None and j[k] is None, k
+    assert set(j["leg_seconds"]) == {"headline_and_exchange_legs"} and j["ranks"][0]["device"] == 0
+    assert wall - 250 * j["ms_per_step"] * 1e-3 < 90, wall
+
+
+def test_bench_plain_run_names_the_leg_options_it_ignores():
+    """the --no-* and leg-size options shape a --full run; a plain run given one says so on stderr (no GPU needed: the start-up is cut
+    short as in test_bench_startup_has_a_time_budget_too)"""
+    env = dict(os.environ, BENCH_TEST_HANG_LEG="startup", BENCH_LEG_BUDGET_S="2")
+    for extra, named in (([], None), (["--crt-channels", "3000000", "--no-dropin"], "--crt-channels, --no-dropin"), (["--full", "--no-dropin"], None)):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True, timeout=120, env=env)
+        assert r.returncode == 0, r.stderr[-1000:]
+        assert ("ignores" in r.stderr) == bool(named) and (named is None or named + " shape the legs of a --full run" in r.stderr), r.stderr[-1000:]
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("extra,cfg", [(["--config", "1"], 1), (["--config", "2"], 2), (["--config", "4"], 4), (["--config", "5"], 5)])
 def test_bench_other_configs_run_on_one_gpu(extra, cfg, tmp_path):
     env = dict(os.environ)
@@ -168,7 +194,7 @@ def test_bench_other_configs_run_on_one_gpu(extra, cfg, tmp_path):
         env["BENCH_FORCE_DIST"] = "1"          # one rank, but through the process group and the RCCL exchange behind the C ABI
         env["BENCH_ALL_EXCHANGES"] = "1"       # ... every hand-over: spectrum rows, whole slot, and (round 4) the block's samples
         env["MASTER_PORT"] = "29617"
-    h, j = _run_bench(["--steps", "20", "--warmup", "5", "--no-crt", "--no-cpu-baseline", "--no-crt-pcie", "--no-next-rows",
+    h, j = _run_bench(["--full", "--steps", "20", "--warmup", "5", "--no-crt", "--no-cpu-baseline", "--no-crt-pcie", "--no-next-rows",
                        "--dropin-blocks", "40"] + extra, tmp_path, env=env)
     assert h["config"]["baseline_config"] == cfg and h["value"] > 0
     assert j["config"]["baseline_config"] == cfg and j["n_gpus"] == 1 and j["value"] > 0
@@ -203,7 +229,7 @@ def test_bench_two_ranks_control_flow_on_one_gpu(args, port, tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "20", "--warmup", "5",
            "--no-cpu-baseline", "--no-dropin", "--detail", str(tmp_path / "detail.json")] + args
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
