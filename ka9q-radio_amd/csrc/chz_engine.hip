@@ -146,22 +146,26 @@ struct Lane {
   float2* buf = nullptr;
 };
 
-// A persistent host thread that issues the launches of a subset of the lanes.  It spins for a short while
-// after each task so that back-to-back chz_run_blocks calls do not pay a wake-up, then sleeps.
+// A persistent host thread that issues the launches of a subset of the lanes.  It spins for about a millisecond
+// after each task so that back-to-back chz_run_blocks calls do not pay a wake-up, then sleeps.  The budget is time, not
+// iterations: a pause instruction takes some 40 to 140 cycles depending on the CPU, and what has to be bridged is the
+// caller's time between two calls (measured around the benchmark's synchronise between warm-up and timed call: 0.1-0.2 ms).
 struct Issuer {
   std::thread th;
   std::mutex m;
   std::condition_variable cv;
   std::atomic<int> state{0};      // 0 idle, 1 task posted, 2 task done, 3 quit
+  std::atomic<int> ready{0};      // the thread is up and has its device set: only then is it given work
   bool sleeping = false;
   std::function<void()> fn;
   void loop() {
     for (;;) {
-      int spins = 0;
+      const auto awake_until = std::chrono::steady_clock::now() + std::chrono::milliseconds(1);
+      unsigned spins = 0;
       for (;;) {
         const int s = state.load(std::memory_order_acquire);
         if (s == 1 || s == 3) break;
-        if (++spins < 20000) { __builtin_ia32_pause(); continue; }
+        if ((++spins & 255u) || std::chrono::steady_clock::now() < awake_until) { __builtin_ia32_pause(); continue; }
         std::unique_lock<std::mutex> lk(m);
         sleeping = true;
         cv.wait(lk, [&] { const int t = state.load(std::memory_order_acquire); return t == 1 || t == 3; });
@@ -265,6 +269,10 @@ struct chz_engine {
   int graph_min_blocks = 32;        // env CHZ_GRAPH_BLOCKS: a replay covers at least this many blocks (drained once per replay)
   // chz_run_blocks: events and issuing threads live as long as the engine
   hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_fork = nullptr, ev_join[CHZ_MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
+  // the eager path joins on the HOST: one timing event in front of each lane's first block and one behind its last, one behind
+  // the demodulator stream's last kernel when the call issued any (tail_issued; two issuing threads may raise it)
+  hipEvent_t ev_begin[CHZ_MAX_LANES] = {nullptr, nullptr, nullptr, nullptr}, ev_end[CHZ_MAX_LANES] = {nullptr, nullptr, nullptr, nullptr}, ev_end_tail = nullptr;
+  int tail_issued = 0;
   std::vector<Issuer*> issuers;
 };
 
@@ -492,6 +500,8 @@ int chz_engine_create(chz_engine** out, int L, int M, int in_type, int device, c
   HIPOK(hipEventCreate(&e->ev_t0)); HIPOK(hipEventCreate(&e->ev_t1));
   HIPOK(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
   for (int i = 0; i < CHZ_MAX_LANES; i++) HIPOK(hipEventCreateWithFlags(&e->ev_join[i], hipEventDisableTiming));
+  for (int i = 0; i < CHZ_MAX_LANES; i++) { HIPOK(hipEventCreate(&e->ev_begin[i])); HIPOK(hipEventCreate(&e->ev_end[i])); }
+  HIPOK(hipEventCreate(&e->ev_end_tail));
   for (int i = 0; i < CHZ_NOTCH_EVENTS; i++) HIPOK(hipEventCreateWithFlags(&e->notch_ev[i], hipEventDisableTiming | hipEventReleaseToDevice));
   {
     int khz = 0;                                        // constant-rate counter, kHz (100 MHz on this family)
@@ -567,6 +577,9 @@ void chz_engine_destroy(chz_engine* e) {
   if (e->ev_t1) hipEventDestroy(e->ev_t1);
   if (e->ev_fork) hipEventDestroy(e->ev_fork);
   for (auto ev : e->ev_join) if (ev) hipEventDestroy(ev);
+  for (auto ev : e->ev_begin) if (ev) hipEventDestroy(ev);
+  for (auto ev : e->ev_end) if (ev) hipEventDestroy(ev);
+  if (e->ev_end_tail) hipEventDestroy(e->ev_end_tail);
   for (auto ev : e->notch_ev) if (ev) hipEventDestroy(ev);
   for (auto& b : e->banks) free_bank(b);
   hipFree(e->ring); hipFree(e->ring16); hipFree(e->energy_part); hipFree(e->clip_part);
@@ -1237,7 +1250,7 @@ static int enqueue_bank(chz_engine* e, int bank, unsigned job, Instr* in, int ch
     mark(in, ts, 6, true);
     if (launch_demod(ts, d, IN_E0(in), IN_E1(in))) return fail(-4, "the demodulator kernel refuses blocks of %d samples", b.olen);
     mark(in, ts, 6, false);
-    if (ts != st) { HIPOK(hipEventRecord(b.ev_tail[slot], ts)); b.tail_used[slot] = true; }
+    if (ts != st) { HIPOK(hipEventRecord(b.ev_tail[slot], ts)); b.tail_used[slot] = true; __atomic_store_n(&e->tail_issued, 1, __ATOMIC_RELAXED); }
   }
   return 0;
 }
@@ -2036,9 +2049,20 @@ int chz_run_blocks(chz_engine* e, unsigned job0, int nblocks, int mode, int inst
   { int r = sync_all(e); if (r) return r; }
   e->input_pending = false;                       // everything written so far is visible to every lane now
   e->notch_have = false;                          // the device is idle: nothing to order the first block behind
+  e->tail_issued = 0;
   hipEvent_t t0 = e->ev_t0, t1 = e->ev_t1, fork_ev = e->ev_fork;
   hipEvent_t* join_ev = e->ev_join;
   Instr in; in.on = instrument != 0 && mode == 0;
+  // The eager path neither forks nor joins on the device.  sync_all() above has drained every stream and the input has an event of
+  // its own, so a fork would order nothing, and each cross-stream link costs latency at both ends of the call (profiles/
+  // run_blocks_fixed_cost.txt).  Every lane starts at once behind a timing event of its own, carries a second one behind its last
+  // block, and the HOST waits for those; total_ms is the span from the earliest start to the latest end.  The device-side fork and
+  // join stay where the lanes must be tied into one stream-ordered unit: graph capture, the eager tail of a graph run, the sharded loop.
+#if CHZ_FWD_BATCH
+  const bool host_join = false;                   // (the batched-pass experiment launches groups of lanes at once and keeps the fork and join)
+#else
+  const bool host_join = mode == 0 && !in.on;
+#endif
   hipStream_t s0 = e->lanes[0].s;
   int done = 0, rc = 0;
   const auto host_t0 = std::chrono::steady_clock::now();
@@ -2083,8 +2107,18 @@ int chz_run_blocks(chz_engine* e, unsigned job0, int nblocks, int mode, int inst
       if ((rc = lanes_join(e, join_ev))) return rc;
     }
   } else {
-    HIPOK(hipEventRecord(t0, s0));
-    if (!in.on && (rc = lanes_fork(e, fork_ev))) return rc;
+    if (!host_join) HIPOK(hipEventRecord(t0, s0));
+    if (!host_join && !in.on && (rc = lanes_fork(e, fork_ev))) return rc;
+    // one block; with the host-side join, the lane's begin event in front of its first block of the call and its end event behind its last
+    auto issue = [&](int b, Instr* ins, NotchTurn* turn) -> int {
+      const unsigned job = job0 + (unsigned)b;
+      const int ln = (int)(job % (unsigned)e->nlanes);
+      if (host_join && b < e->nlanes) HIPOK(hipEventRecord(e->ev_begin[ln], e->lanes[ln].s));
+      const int r = enqueue_step(e, job, ins, turn, b);
+      if (r) return r;
+      if (host_join && b >= nblocks - e->nlanes) HIPOK(hipEventRecord(e->ev_end[ln], e->lanes[ln].s));
+      return 0;
+    };
 #if CHZ_FWD_BATCH
     {   // EXPERIMENT: CHZ_FWD_BATCH_N = 2 or 4 blocks per launch (forward transform only: every bank must be idle); 4 / N batches in flight
       static const int B = [] { const char* v = CHZ_XENV("CHZ_FWD_BATCH_N"); const int k = v ? atoi(v) : 0; return (k == 2 || k == 4) ? k : 0; }();
@@ -2101,14 +2135,24 @@ int chz_run_blocks(chz_engine* e, unsigned job0, int nblocks, int mode, int inst
     // Blocks of different lanes are independent launch sequences.  A single host thread issues ~5 launches per block at
     // ~3 us each, which bounds the small configurations -- so the lanes are split over CHZ_ENQ_THREADS host threads
     // (default 2; 1 = issue from the caller only): the caller takes its share, persistent issuers take the rest.
+    // The split is static (by lane) and the notch hand-over makes every block wait for its predecessor's launch, so a thread that
+    // is late holds up everybody.  Hence: the issuers are started by the engine's FIRST eager call of any size (a warm-up call pays
+    // for the thread, measured ~0.2 ms to its first launch, not the first long call), and a call is only split once every issuer has
+    // reported ready -- until then the caller issues alone.  Calls shorter than two rounds of the lanes stay with the caller: the
+    // hand-over costs more than the few launches it would take off it (the threshold is round 2's, for the steady state; at one
+    // block -- what a real-time caller issues per 20 ms -- there is nothing to split).
     const int T = issue_threads();
-    if (T > 1 && !in.on && done == 0 && e->nlanes >= T && nblocks >= 2 * e->nlanes) {
+    if (T > 1 && !in.on && e->nlanes >= T) {
       while ((int)e->issuers.size() < T - 1) {
         Issuer* is = new Issuer();
         const int dev = e->device;
-        is->th = std::thread([is, dev] { (void)hipSetDevice(dev); is->loop(); });
+        is->th = std::thread([is, dev] { (void)hipSetDevice(dev); is->ready.store(1, std::memory_order_release); is->loop(); });
         e->issuers.push_back(is);
       }
+    }
+    bool issuers_ready = T > 1 && (int)e->issuers.size() >= T - 1;
+    for (int t = 1; t < T && issuers_ready; t++) issuers_ready = e->issuers[(size_t)(t - 1)]->ready.load(std::memory_order_acquire) != 0;
+    if (issuers_ready && !in.on && done == 0 && e->nlanes >= T && nblocks >= 2 * e->nlanes) {
       NotchTurn turn;
       std::vector<int> rcs((size_t)T, 0);
       std::vector<std::string> errs((size_t)T);
@@ -2116,7 +2160,7 @@ int chz_run_blocks(chz_engine* e, unsigned job0, int nblocks, int mode, int inst
         for (int b = done; b < nblocks && !rcs[(size_t)t]; b++) {
           const unsigned job = job0 + (unsigned)b;
           if ((int)(job % (unsigned)e->nlanes) % T != t) continue;
-          if ((rcs[(size_t)t] = enqueue_step(e, job, nullptr, &turn, b))) { errs[(size_t)t] = g_err; turn.abort.store(1); }
+          if ((rcs[(size_t)t] = issue(b, nullptr, &turn))) { errs[(size_t)t] = g_err; turn.abort.store(1); }
         }
       };
       for (int t = 1; t < T; t++) e->issuers[(size_t)(t - 1)]->post([&work, t] { work(t); });
@@ -2126,22 +2170,45 @@ int chz_run_blocks(chz_engine* e, unsigned job0, int nblocks, int mode, int inst
       for (Bank& b : e->banks) b.last_slot = (int)((job0 + (unsigned)nblocks - 1u) % CHZ_ND);            // what a single issuer would have left
       done = nblocks;
     }
-    for (; done < nblocks; done++) if ((rc = enqueue_step(e, job0 + (unsigned)done, &in))) return rc;
-    if (!in.on && (rc = lanes_join(e, join_ev))) return rc;
+    for (; done < nblocks; done++) if ((rc = issue(done, &in, nullptr))) return rc;
+    if (!host_join && !in.on && (rc = lanes_join(e, join_ev))) return rc;
   }
-  if (e->tail && !in.on) {          // the demodulators of the last blocks belong to the run (ev_join[0] is free: lanes join from 1 up)
-    HIPOK(hipEventRecord(join_ev[0], e->tail));
-    HIPOK(hipStreamWaitEvent(s0, join_ev[0], 0));
+  double enqueue_ms = 0.0, total_ms = 0.0;
+  if (host_join) {
+    // the demodulators of the last blocks belong to the run -- when this call issued any: an idle demodulator stream is not waited for
+    const bool tail = __atomic_load_n(&e->tail_issued, __ATOMIC_RELAXED) != 0;
+    if (tail) HIPOK(hipEventRecord(e->ev_end_tail, e->tail));
+    enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count();
+    const int used = nblocks < e->nlanes ? nblocks : e->nlanes;            // lanes with a block of this call: job0 .. job0 + used - 1
+    for (int i = 0; i < used; i++) HIPOK(hipEventSynchronize(e->ev_end[(job0 + (unsigned)i) % (unsigned)e->nlanes]));
+    if (tail) HIPOK(hipEventSynchronize(e->ev_end_tail));
+    HIPOK(hipGetLastError());
+    if (timing && used > 0) {
+      hipEvent_t ref = e->ev_begin[job0 % (unsigned)e->nlanes];
+      float lo = 0.f, hi = 0.f, d = 0.f;                                   // ms after `ref`: the earliest begin, the latest end
+      for (int i = 0; i < used; i++) {
+        const unsigned ln = (job0 + (unsigned)i) % (unsigned)e->nlanes;
+        if (i) { HIPOK(hipEventElapsedTime(&d, ref, e->ev_begin[ln])); if (d < lo) lo = d; }
+        HIPOK(hipEventElapsedTime(&d, ref, e->ev_end[ln])); if (d > hi) hi = d;
+      }
+      if (tail) { HIPOK(hipEventElapsedTime(&d, ref, e->ev_end_tail)); if (d > hi) hi = d; }
+      total_ms = (double)hi - (double)lo;
+    }
+  } else {
+    if (e->tail && !in.on) {          // the demodulators of the last blocks belong to the run (ev_join[0] is free: lanes join from 1 up)
+      HIPOK(hipEventRecord(join_ev[0], e->tail));
+      HIPOK(hipStreamWaitEvent(s0, join_ev[0], 0));
+    }
+    HIPOK(hipEventRecord(t1, s0));
+    enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count();
+    HIPOK(hipEventSynchronize(t1));
+    HIPOK(hipGetLastError());
+    if (timing) { float ms = 0; HIPOK(hipEventElapsedTime(&ms, t0, t1)); total_ms = ms; }
   }
-  HIPOK(hipEventRecord(t1, s0));
-  const double enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count();
-  HIPOK(hipEventSynchronize(t1));
-  HIPOK(hipGetLastError());
   if (timing) {
     memset(timing, 0, sizeof *timing);
     timing->enqueue_ms = enqueue_ms;
-    float ms = 0; HIPOK(hipEventElapsedTime(&ms, t0, t1));
-    timing->total_ms = ms; timing->blocks = nblocks;
+    timing->total_ms = total_ms; timing->blocks = nblocks;
     double* acc[7] = {&timing->first_ms, &timing->cols_ms, &timing->rows_ms, &timing->notch_ms, &timing->chan_ms, &timing->fix_ms, &timing->demod_ms};
     int* cnt[7] = {&timing->first_n, &timing->cols_n, &timing->rows_n, &timing->notch_n, &timing->chan_n, &timing->fix_n, &timing->demod_n};
     for (size_t i = 0; i < in.kind.size(); i++) {
