@@ -265,7 +265,6 @@ struct chz_engine {
   std::vector<Bank> banks;
   hipGraphExec_t graph = nullptr; unsigned graph_job0 = 0; int graph_blocks = 0;
   int capture_blocks = 0;           // blocks of the capture in progress (the last one moves the ticket base on)
-  bool graph_notch_event = false;   // env CHZ_GRAPH_NOTCH=event: order the notches of captured blocks by HIP events (round 2's way)
   int graph_min_blocks = 32;        // env CHZ_GRAPH_BLOCKS: a replay covers at least this many blocks (drained once per replay)
   // chz_run_blocks: events and issuing threads live as long as the engine
   hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_fork = nullptr, ev_join[CHZ_MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
@@ -339,19 +338,10 @@ int chz_gather_descriptor(int in_type, int master_bins, int P, int shift, int ou
 // hipExtStreamCreateWithCUMask with EVERY compute unit enabled -- such a stream is given a queue of its own.  The transform lanes keep
 // plain streams: they are exactly the four the runtime has queues for (with every stream masked one driver-command bench run hung: a CU-masked
 // stream is a BLOCKING stream, see chz_engine_create -- masked lanes are only to be had with the notch ordered by HIP events).
-// EXPERIMENT knob on top: CHZ_TAIL_CUS=n gives the demodulator stream n of the compute units to itself (spread
-// evenly over the XCDs) and the transform lanes the others -- the partition itself buys nothing (4.20-4.33 ms), see the decision record.
 // ---- options (round 6).  Dispatch thresholds and test hooks are set through the C ABI -- chz_set_option(name, value) before the engine is
 // created -- not through the environment: the shipped libraries read the operator's variables only (CHZ_PLAN,
 // CHZ_STREAMS, CHZ_NOTCH_ORDER, CHZ_OWN_QUEUES, CHZ_RCCL_LIB, CHZ_COMM_TIMEOUT_S and the drop-in's KA9Q_HIP_*); the Python test mirror
-// (ka9q-radio_amd/engine.py) and the C test drivers translate the CHZ_* names the tests use into these calls.  A/B EXPERIMENT hooks
-// (CHZ_TAIL_CUS, CHZ_NO_TWFULL, CHZ_AGC_PEAK, CHZ_CHAN_WPB, CHZ_FWD_BATCH_N, CHZ_GRAPH_NOTCH ...) exist only in builds with -DCHZ_EXPERIMENTS
-// (the A/B targets of the Makefile): CHZ_XENV() is getenv() there and a null pointer in the shipped library.
-#ifdef CHZ_EXPERIMENTS
-#define CHZ_XENV(name) getenv(name)
-#else
-#define CHZ_XENV(name) ((const char*)nullptr)
-#endif
+// (ka9q-radio_amd/engine.py) and the C test drivers translate the CHZ_* names the tests use into these calls.
 struct ChzOptions {
   int chan_stage = -1;        // chan_ifft rows staged through LDS: -1 auto (launches of >= 16384 channels), 0 never, 1 always
   int noise_energy = -1;      // |X|^2 image for the noise windows: -1 auto, 0 never, 1 always
@@ -392,17 +382,15 @@ extern "C" int chz_set_option(const char* name, const char* value) {
 }
 static ChzOptions options() { std::lock_guard<std::mutex> lk(g_opt_mu); return g_opt; }
 
-static int tail_cus() { static const int n = [] { const char* v = CHZ_XENV("CHZ_TAIL_CUS"); const int k = v ? atoi(v) : 0; return (k > 0 && k < 256) ? k : 0; }(); return n; }
 // CHZ_OWN_QUEUES: 0 plain streams everywhere (rounds 1-4), 1 (default) the demodulator stream and the PCM copy stream, 2 every stream the
 // engine launches kernels on
 static int own_queues() { static const int m = [] { const char* v = getenv("CHZ_OWN_QUEUES"); const int k = v ? atoi(v) : 1; return (k >= 0 && k <= 4) ? k : 1; }(); return m; }
 static hipError_t stream_create_masked(hipStream_t* s, bool tail) {
 #ifndef HIPEMU
-  const int n = tail_cus();
   // (round 6 A/B) 3 / 4: the demodulator and PCM copy streams as NON-BLOCKING streams of another priority (3 = highest, 4 = lowest): the runtime keeps
   // a pool of hardware queues per priority, so such a stream does not share a queue with the four normal-priority lanes either -- and, unlike a
   // CU-masked stream, it IS a hipStreamNonBlocking stream (scripts/micro/masked_stream_blocking.hip, profiles/r06_masked_stream_blocking.txt)
-  if (n == 0 && tail && own_queues() >= 3) {
+  if (tail && own_queues() >= 3) {
     int lo = 0, hi = 0;
     if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi) {
       const hipError_t r = hipStreamCreateWithPriority(s, hipStreamNonBlocking, own_queues() == 3 ? hi : lo);
@@ -411,14 +399,11 @@ static hipError_t stream_create_masked(hipStream_t* s, bool tail) {
     }
     return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
   }
-  if (n > 0 || own_queues() == 2 || (own_queues() == 1 && tail)) {
+  if (own_queues() == 2 || (own_queues() == 1 && tail)) {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0 && cus <= 1024) {
       uint32_t mask[32] = {};
-      for (int i = 0; i < cus; i++) {
-        const bool t = n > 0 && (((i + 1) * n) / cus > (i * n) / cus);      // n of the units, evenly spread
-        if (n == 0 || t == tail) mask[i / 32] |= 1u << (i % 32);
-      }
+      for (int i = 0; i < cus; i++) mask[i / 32] |= 1u << (i % 32);
       const hipError_t r = hipExtStreamCreateWithCUMask(s, (uint32_t)((cus + 31) / 32), mask);
       if (r == hipSuccess) return r;
       (void)hipGetLastError();                       // a runtime without the extension: plain streams
@@ -509,7 +494,6 @@ int chz_engine_create(chz_engine** out, int L, int M, int in_type, int device, c
     const double ms = opt.notch_wait_ms;
     e->notch_max_wait = (long long)(ms * (double)khz);
   }
-  if (const char* gn = CHZ_XENV("CHZ_GRAPH_NOTCH")) e->graph_notch_event = strcmp(gn, "event") == 0;
   e->graph_min_blocks = opt.graph_blocks;
   if (const char* no = getenv("CHZ_NOTCH_ORDER")) e->notch_order = strcmp(no, "event") == 0 ? 1 : (strcmp(no, "unordered-timing-only") == 0 ? 2 : 0);
   // (round 6) CU-masked LANES are blocking streams -- hipExtStreamCreateWithCUMask takes no flags and makes hipStreamDefault streams, ordered with the
@@ -517,7 +501,7 @@ int chz_engine_create(chz_engine** out, int L, int M, int in_type, int device, c
   // hipMemcpy / hipMemset of this engine, torch's default stream in bench.py) lands between the two launches: the waiter spins for a kernel that
   // queues behind the null-stream operation, which waits for the waiter.  That was round 5's bench run that never came back (reproducer:
   // scripts/micro/masked_stream_blocking.hip, profiles/r06_masked_stream_blocking.txt).  Masked lanes therefore order the notch by HIP events, always.
-  if ((own_queues() == 2 || tail_cus() > 0) && e->notch_order == 0) e->notch_order = 1;
+  if (own_queues() == 2 && e->notch_order == 0) e->notch_order = 1;
   HIPOK(hipHostMalloc((void**)&e->notch_err, sizeof(unsigned), hipHostMallocMapped));
   *e->notch_err = 0;
   for (int i = 0; i < e->nlanes; i++) {
@@ -825,9 +809,8 @@ static int enqueue_notch(chz_engine* e, int slot, hipStream_t st, Instr* in, Not
     }
   }
   int rc = 0;
-  // inside a capture the ticket is relative to a device word (one captured node serves every replay); CHZ_GRAPH_NOTCH=event
-  // keeps round 2's event chain inside graphs
-  const bool by_event = e->notch_order == 1 || (capturing && e->graph_notch_event);
+  // inside a capture the ticket is relative to a device word (one captured node serves every replay)
+  const bool by_event = e->notch_order == 1;
   do {
     if (by_event && e->notch_have && !capture_first && e->nlanes > 1) {
       hipError_t he = hipStreamWaitEvent(st, e->notch_ev[(e->notch_seq - 1u) % CHZ_NOTCH_EVENTS], 0);
@@ -977,35 +960,17 @@ static int enqueue_forward(chz_engine* e, unsigned job, Instr* in, NotchTurn* tu
     ColsParams b{};
     b.in = lbuf; b.in_len = 0; b.in_start = 0; b.out = lbuf; b.rows = p.Ra; b.inner = p.Nc; b.T = p.T2;
     b.padk = p.padk2; b.tw_sub = e->tw_sub_b; b.tw_tile = e->tw2_tile; b.tw_col = e->tw2_col;
-    if (!CHZ_XENV("CHZ_NO_TWFULL")) b.tw_full = e->tw2_full;
-    int grid2 = p.grid2;
-#if CHZ_XCD_AFFINE
-    // (experiment build: axis b of a three-axis plan only -- a complex master's first axis goes through launch_cols above, untouched... and
-    //  would be remapped too: this build serves REAL three-axis masters, which is what the experiment measures)
-    const int ncomp = (p.Ra + p.ka_shift + p.Ta - 1) / p.Ta;
-    if (ncomp > 8) return fail(-4, "the XCD-affine experiment build places at most 8 components (plan has %d)", ncomp);
-    b.xa = XcdAffine{CHZ_XCD_AFFINE, p.Ta, p.ka_shift, (int)((job * (unsigned)ncomp) & 7u), ncomp};
-    grid2 = 8 * p.Ta * (p.Nc / p.T2);
-#endif
+    b.tw_full = e->tw2_full;
     mark(in, st, 1, true);
-    if (launch_cols(p.rb, grid2, p.block2, p.lds2, st, b, IN_E0(in), IN_E1(in))) return fail(-4, "no kernel for axis b");
+    if (launch_cols(p.rb, p.grid2, p.block2, p.lds2, st, b, IN_E0(in), IN_E1(in))) return fail(-4, "no kernel for axis b");
     mark(in, st, 1, false);
   }
   RowsParams c{};
   c.lay = SpecLayout{p.Na, p.spec_pitch, p.spec_off}; c.ka_shift = p.ka_shift;
   c.buf = lbuf; c.spec = e->spec[slot]; c.Ra = p.Ra; c.Na = p.Na; c.Nb = p.Nb; c.Ta = p.Ta; c.ld = p.ld3;
   c.padg = p.padg3; c.N = p.N; c.mirror = e->in_type == CHZ_REAL; c.tw_sub = e->tw_sub_c;
-  int grid3 = p.grid3;
-#if CHZ_XCD_AFFINE
-  {
-    const int ncomp = (p.Ra + p.ka_shift + p.Ta - 1) / p.Ta;
-    if (ncomp > 8 || p.Nb <= 1 || e->in_type != CHZ_REAL) return fail(-4, "the XCD-affine experiment build serves REAL three-axis masters with at most 8 a-tiles");
-    c.xa = XcdAffine{CHZ_XCD_AFFINE, p.Ta, p.ka_shift, (int)((job * (unsigned)ncomp) & 7u), ncomp};
-    grid3 = 8 * p.Nb;
-  }
-#endif
   // K2 inside this pass (short lists ordered by the device ticket): the launch is then what has to go out in block order
-  const bool by_event = e->notch_order == 1 || (capturing && e->graph_notch_event);
+  const bool by_event = e->notch_order == 1;
   const bool fold = e->n_notch > 0 && e->notch_fold.n > 0 && !by_event && e->notch_order != 2;
   if (fold) {
     if (turn) {
@@ -1022,7 +987,7 @@ static int enqueue_forward(chz_engine* e, unsigned job, Instr* in, NotchTurn* tu
       c.nf.adv = seq == e->capture_blocks - 1 ? (unsigned)e->capture_blocks : 0u;
     } else if (ticket) { c.nf.ver = e->notch_ver; c.nf.seq = e->notch_tickets; }
     mark(in, st, 2, true);
-    const int lr = launch_rows(p.rc, grid3, p.block3, p.lds3, st, c, IN_E0(in), IN_E1(in));
+    const int lr = launch_rows(p.rc, p.grid3, p.block3, p.lds3, st, c, IN_E0(in), IN_E1(in));
     mark(in, st, 2, false);
     if (!lr && ticket && !capturing) e->notch_tickets++;           // taken only by a launch that went out
     if (turn) {
@@ -1033,40 +998,10 @@ static int enqueue_forward(chz_engine* e, unsigned job, Instr* in, NotchTurn* tu
     return 0;
   }
   mark(in, st, 2, true);
-  if (launch_rows(p.rc, grid3, p.block3, p.lds3, st, c, IN_E0(in), IN_E1(in))) return fail(-4, "no kernel for axis c");
+  if (launch_rows(p.rc, p.grid3, p.block3, p.lds3, st, c, IN_E0(in), IN_E1(in))) return fail(-4, "no kernel for axis c");
   mark(in, st, 2, false);
   return enqueue_notch(e, slot, st, in, turn, seq, capture_first, capturing);
 }
-
-#if CHZ_FWD_BATCH
-// EXPERIMENT (see chz_kernels.h): the forward transform of blocks job .. job+B-1 (B = 2 or 4, job a multiple of B) as three launches of
-// B x the grid, on `st`; block y uses lane (job + y) % 4's intermediate buffer and spectrum slot (job + y) % 4.  REAL three-axis masters,
-// float input, no notch list (timing only).
-static int enqueue_forward_batch(chz_engine* e, unsigned job, int B, hipStream_t st) {
-  const FwdPlan& p = e->plan;
-  if (e->blue || e->in_type != CHZ_REAL || p.Nb <= 1 || e->ring16 || e->n_notch > 0 || e->nlanes != 4) return fail(-4, "the batched-pass experiment serves REAL three-axis masters on 4 lanes without a notch list");
-  FirstRealParams a{};
-  a.ring = e->ring; a.ring_len = e->ring_len; a.inner = p.inner; a.T = p.T1; a.Ra = p.Ra; a.padk = p.padk1;
-  a.tw_sub = e->tw_sub_a; a.tw_tile = e->tw1_tile; a.tw_col = e->tw1_col; a.nbatch = B;
-  ColsParams b{};
-  b.in_len = 0; b.in_start = 0; b.rows = p.Ra; b.inner = p.Nc; b.T = p.T2; b.padk = p.padk2;
-  b.tw_sub = e->tw_sub_b; b.tw_tile = e->tw2_tile; b.tw_col = e->tw2_col; b.tw_full = e->tw2_full; b.nbatch = B;
-  RowsParams c{};
-  c.lay = SpecLayout{p.Na, p.spec_pitch, p.spec_off}; c.ka_shift = p.ka_shift;
-  c.Ra = p.Ra; c.Na = p.Na; c.Nb = p.Nb; c.Ta = p.Ta; c.ld = p.ld3; c.padg = p.padg3; c.N = p.N; c.mirror = 1; c.tw_sub = e->tw_sub_c; c.nbatch = B;
-  for (int y = 0; y < B; y++) {
-    const unsigned j = job + (unsigned)y;
-    a.bstart[y] = (long)(((unsigned long long)j * (unsigned long long)e->L) % (unsigned long long)((long)e->ring_blocks * e->L)) * e->per;
-    float2* lb = e->lanes[j % 4u].buf;
-    a.bbuf[y] = lb; b.bbuf[y] = lb; c.bbuf[y] = lb; c.bspec[y] = e->spec[j % CHZ_ND];
-  }
-  a.start = a.bstart[0]; a.buf = a.bbuf[0]; b.in = b.bbuf[0]; b.out = b.bbuf[0]; c.buf = c.bbuf[0]; c.spec = c.bspec[0];
-  if (launch_first_real(p.ra, dim3((unsigned)p.grid1, (unsigned)B), p.block1, p.lds1, st, a)) return fail(-4, "no kernel for axis a");
-  if (launch_cols(p.rb, dim3((unsigned)p.grid2, (unsigned)B), p.block2, p.lds2, st, b)) return fail(-4, "no kernel for axis b");
-  if (launch_rows(p.rc, dim3((unsigned)p.grid3, (unsigned)B), p.block3, p.lds3, st, c)) return fail(-4, "no kernel for axis c");
-  return 0;
-}
-#endif
 
 // output image of one slot; a sample is one float (REAL banks) or one float2
 static inline size_t bank_sample_bytes(const Bank& b) { return b.out_real ? sizeof(float) : sizeof(float2); }
@@ -1196,7 +1131,7 @@ static int enqueue_bank(chz_engine* e, int bank, unsigned job, Instr* in, int ch
   c.fine = b.fine ? b.fine + so : nullptr; c.power = b.power ? b.power + so : nullptr; c.job = job;
   if (b.fine) fine_launch(c, 1 + e->L / (e->M - 1), job);
   // the AGC's first look at the block rides in the channel kernel's epilogue when the rows pass through LDS anyway (large launches) and the
-  // lane-per-channel demodulator follows (CHZ_AGC_PEAK=0: A/B knob, the demodulator then walks the block twice as before)
+  // lane-per-channel demodulator follows
   // (only when somebody will use them: linear channels outside the coherent modes, served by the lane-per-channel demodulator)
   const bool peaks = b.agc_peak && whole_bank && c.stage && !b.g.any && !b.out_real && (c.fine || c.power) && b.dm_on > 0 && b.dm_auto &&
                      b.dm_lin > b.dm_pll_lin && (e->demod_wave == 0 || (e->demod_wave < 0 && b.dm_lin >= 65536));
@@ -1295,11 +1230,7 @@ int chz_set_notches_alpha(chz_engine* e, const int* bins, const double* alpha, i
   { const ChzOptions o = options(); if (o.fault_ticket_skew && o.allow_fault_injection) e->notch_tickets = (unsigned)o.fault_ticket_skew; }
   e->n_notch = n;
   e->notch_fold = RowsNotch{};
-  const char* nf = e->opt_notch_fold ? nullptr : "0";
-#if CHZ_XCD_AFFINE
-  nf = "0";        // the experiment builds remap blockIdx inside fwd_rows; the owner table of the folded notch is made for the default mapping
-#endif
-  if (!e->blue && !(nf && nf[0] == '0') && n <= CHZ_NOTCH_INLINE) {
+  if (!e->blue && e->opt_notch_fold && n <= CHZ_NOTCH_INLINE) {
     std::vector<NotchOwn> own;
     if (rows_notch_fill(e->notch_fold, own, e->plan, e->in_type == CHZ_REAL, bins, n)) {       // false leaves n = 0: the kernel serves the list
       HIPOK(hipMalloc((void**)&e->notch_own, sizeof(NotchOwn) * own.size()));
@@ -1711,7 +1642,7 @@ int chz_bank_set_demod(chz_engine* e, int bank, unsigned job, int ch0, int n, co
     HIPOK(hipMemcpy(b.dm_ext, fresh.data(), sizeof(DemodExt) * (size_t)b.cap, hipMemcpyHostToDevice));
     drop_graph(e);
   }
-  if (!b.agc_peak && (e->demod_wave == 0 || (e->demod_wave < 0 && b.cap >= 65536)) && !(CHZ_XENV("CHZ_AGC_PEAK") && CHZ_XENV("CHZ_AGC_PEAK")[0] == '0')) {
+  if (!b.agc_peak && (e->demod_wave == 0 || (e->demod_wave < 0 && b.cap >= 65536))) {
     HIPOK(hipMalloc((void**)&b.agc_peak, sizeof(double) * (size_t)CHZ_ND * b.cap));
     HIPOK(hipMemset(b.agc_peak, 0, sizeof(double) * (size_t)CHZ_ND * b.cap));
     HIPOK(hipDeviceSynchronize());
@@ -2058,11 +1989,7 @@ int chz_run_blocks(chz_engine* e, unsigned job0, int nblocks, int mode, int inst
   // run_blocks_fixed_cost.txt).  Every lane starts at once behind a timing event of its own, carries a second one behind its last
   // block, and the HOST waits for those; total_ms is the span from the earliest start to the latest end.  The device-side fork and
   // join stay where the lanes must be tied into one stream-ordered unit: graph capture, the eager tail of a graph run, the sharded loop.
-#if CHZ_FWD_BATCH
-  const bool host_join = false;                   // (the batched-pass experiment launches groups of lanes at once and keeps the fork and join)
-#else
   const bool host_join = mode == 0 && !in.on;
-#endif
   hipStream_t s0 = e->lanes[0].s;
   int done = 0, rc = 0;
   const auto host_t0 = std::chrono::steady_clock::now();
@@ -2093,7 +2020,7 @@ int chz_run_blocks(chz_engine* e, unsigned job0, int nblocks, int mode, int inst
       e->graph_blocks = cycle; e->graph_job0 = phase;
     }
     for (Bank& b : e->banks) { int r = refresh_all_bulk(e, b); if (r) return r; }
-    const bool graph_ticket = e->n_notch > 0 && e->nlanes > 1 && e->notch_order == 0 && !e->graph_notch_event;
+    const bool graph_ticket = e->n_notch > 0 && e->nlanes > 1 && e->notch_order == 0;
     if (graph_ticket)            // captured tickets count from here (the device is idle: sync_all above)
       HIPOK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e->notch_ver + 2), (int)e->notch_tickets, 1, s0));
     HIPOK(hipEventRecord(t0, s0));
@@ -2119,19 +2046,6 @@ int chz_run_blocks(chz_engine* e, unsigned job0, int nblocks, int mode, int inst
       if (host_join && b >= nblocks - e->nlanes) HIPOK(hipEventRecord(e->ev_end[ln], e->lanes[ln].s));
       return 0;
     };
-#if CHZ_FWD_BATCH
-    {   // EXPERIMENT: CHZ_FWD_BATCH_N = 2 or 4 blocks per launch (forward transform only: every bank must be idle); 4 / N batches in flight
-      static const int B = [] { const char* v = CHZ_XENV("CHZ_FWD_BATCH_N"); const int k = v ? atoi(v) : 0; return (k == 2 || k == 4) ? k : 0; }();
-      bool idle = true;
-      for (const Bank& bk : e->banks) idle = idle && bk.active == 0;
-      if (B && idle && !in.on && job0 % (unsigned)B == 0) {
-        for (; done + B <= nblocks; done += B) {
-          const unsigned job = job0 + (unsigned)done;
-          if ((rc = enqueue_forward_batch(e, job, B, e->lanes[(job / (unsigned)B) % (unsigned)(4 / B)].s))) return rc;
-        }
-      }
-    }
-#endif
     // Blocks of different lanes are independent launch sequences.  A single host thread issues ~5 launches per block at
     // ~3 us each, which bounds the small configurations -- so the lanes are split over CHZ_ENQ_THREADS host threads
     // (default 2; 1 = issue from the caller only): the caller takes its share, persistent issuers take the rest.

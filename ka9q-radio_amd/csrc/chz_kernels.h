@@ -150,9 +150,6 @@ struct FirstRealParams {
   unsigned long long* energy_part;   // [grid * waves] or nullptr
   unsigned* clip_part;               // [grid * waves]
   int new_from;
-#if CHZ_FWD_BATCH
-  int nbatch; long bstart[4]; float2* bbuf[4];     // blockIdx.y picks the block's window start and intermediate buffer
-#endif
 };
 
 // A/B of the north star's "wavefront-shuffle twiddles" (build with -DCHZ_TW_SHUFFLE=1; tiles of T = 16 columns only): the epilogue's
@@ -171,14 +168,6 @@ template <int N_> __device__ __forceinline__ float row_shr16(float v) {
 #endif
 }
 
-// EXPERIMENT (round 4, build variant `make xcdaffine`, -DCHZ_XCD_AFFINE=1; the shipped library carries none of it).  The one
-// byte-saving idea left for the forward transform: make fwd_rows read what fwd_cols wrote out of the SAME XCD's L2.  fwd_rows'
-// workgroup (kb, a-tile) reads rows ka of its a-tile at one kb over all nc; fwd_cols' workgroup (ka, column tile) writes every kb of
-// its columns -- so producers and consumers form one connected component per a-tile (5 for config 3: ka in [16c - 12, 16c + 4)).
-// Placement: the dispatcher is observed to put block b on XCD b % 8 (MI355X_MICROARCH.md), so both passes launch 8 x (work per
-// component) blocks, block b serves component (b % 8 - rot) mod 8 and leaves at once if that component does not exist; `rot`
-// advances by ncomp per block so consecutive blocks in flight load different XCDs.  fwd_cols then stores PLAIN (the lines stay
-// in its XCD's L2; write-through stores drop them).  Decision record: DESIGN.md section 7, profiles/r04_xcd_affine.txt.
 // Wavefronts per SIMD the lane-per-channel passes are compiled for (the second __launch_bounds__ argument is HIP's minimum number of
 // wavefronts per execution unit).  Both want ~235 VGPRs; at 3 wavefronts the compiler gets 168 and spills the rest to scratch.  Measured
 // at 1.5 M channels (round 4): demod_fm_lanes 2.28 -> 2.07 ns per channel with 3 (its walks are latency-bound, the spills sit outside the
@@ -189,42 +178,14 @@ template <int N_> __device__ __forceinline__ float row_shr16(float v) {
 #ifndef CHZ_LIN_WAVES
 #define CHZ_LIN_WAVES 2             // demod_lin_lanes: the compiler takes 165 VGPRs with this bound = 3 wavefronts per SIMD (A/B build: -DCHZ_LIN_WAVES=4 caps it at 128)
 #endif
-#ifndef CHZ_PLL_UNROLL
-#define CHZ_PLL_UNROLL 1            // pll_lanes: samples read / stepped / written per group (A/B build: make pllu4)
-#endif
-#ifndef CHZ_LIN_UNROLL
-#define CHZ_LIN_UNROLL 4            // demod_lin_lanes' final pass: samples read / stepped / written per group (1 = round 4's loop; measured at 1.5 M channels on one
-                                    // box, every stream on its own queue: 1 -> 4.28, 4 -> 4.07, 8 -> 4.06 ms per block, PCM bit-identical; A/B: make linu1 / linu8)
-#endif
+constexpr int CHZ_LIN_UNROLL = 4;   // demod_lin_lanes' final pass, demod_fm_lanes' output pass: samples read / stepped / written per group (measured at 1.5 M channels on one
+                                    // box, every stream on its own queue: 1 -> 4.28, 4 -> 4.07, 8 -> 4.06 ms per block, PCM bit-identical)
 #ifndef CHZ_LIN_PACKED_STORE
 #define CHZ_LIN_PACKED_STORE 1      // demod_lin_lanes: mono S16 rows leave as 8-byte words (A/B build: -DCHZ_LIN_PACKED_STORE=0)
 #endif
 #ifndef CHZ_FM_WAVES
 #define CHZ_FM_WAVES 3
 #endif
-#ifndef CHZ_FM_DISC_UNROLL
-#define CHZ_FM_DISC_UNROLL 1        // demod_fm_lanes: samples whose discriminator phases (double atan2) are computed side by side.  Measured at 1.5 M channels
-                                    // (round 6, profiles/r06_fm_disc_unroll.txt; A/B builds: make ../libchz_hip_fmd2.so, _fmd4.so, _fmd8.so): 1 -> 1.93-1.98 ns per
-                                    // channel, 2 -> 1.99-2.01, 4 -> 2.13-2.17, 8 -> 2.49-2.50 (4 at 2 wavefronts per SIMD, no spills: 1.91-1.93): the pass is
-                                    // bound by vector ISSUE (~300 instructions per sample, a third of them the atan2), not by the latency of its chains --
-                                    // overlapping the chains buys nothing and the extra live registers cost spills.  Ships 1 = round 5's loop.
-#endif
-#ifndef CHZ_XCD_AFFINE
-#define CHZ_XCD_AFFINE 0
-#endif
-// EXPERIMENT build (round 5, -DCHZ_FWD_BATCH=1, ../libchz_hip_batch.so): the three forward passes of 2 or 4 CONSECUTIVE blocks as one grid
-// each (blockIdx.y = the block within the batch): 4 x the wavefronts per launch, a third of the launches.  Decision record: DESIGN.md section 7.
-#ifndef CHZ_FWD_BATCH
-#define CHZ_FWD_BATCH 0
-#endif
-// (the block's pointers are picked with compile-time indices: writing to the by-value parameter struct, or indexing its arrays with
-//  blockIdx.y, sends the whole struct through scratch memory -- measured: every pass 3.7 x slower, batched or not)
-#if CHZ_FWD_BATCH
-#define CHZ_BSEL(arr, dflt) (p.nbatch > 1 ? (blockIdx.y == 0 ? arr[0] : blockIdx.y == 1 ? arr[1] : blockIdx.y == 2 ? arr[2] : arr[3]) : (dflt))
-#else
-#define CHZ_BSEL(arr, dflt) (dflt)
-#endif
-struct XcdAffine { int on, Ta, shift, rot, ncomp; };
 
 struct ColsParams {
   const float2* in;       // in[(row*NP + n)*inner + col]  (+ ring wrap when in_len != 0)
@@ -240,10 +201,6 @@ struct ColsParams {
   const float2* tw_col;   // [NP][T]       W_(NP*inner)^(k * t)
   const float2* tw_full;  // [NP][inner] W_(NP*inner)^(k * col), or nullptr: one load and no product per output (axis b: the table
                           // is Nb*Nc entries and L2-resident; axis a of a complex master would need N entries and keeps the two factors)
-  XcdAffine xa;           // experiment build only (CHZ_XCD_AFFINE): XCD-affine placement of the axis-b pass
-#if CHZ_FWD_BATCH
-  int nbatch; float2* bbuf[4];
-#endif
 };
 
 // Spectrum storage: bin k = ka + Na*x lives at  spec[x*pitch + off + ka].  pitch = Na, off = 0 is
@@ -301,11 +258,7 @@ struct RowsParams {
   long N;                 // full transform length
   int mirror;             // 1: real master (bins N/2+1, conj-mirror store); 0: complex master
   const float2* tw_sub;   // [R2][R1] W_Nc^(j*k1)
-  XcdAffine xa;           // experiment build only (CHZ_XCD_AFFINE)
   RowsNotch nf;           // K2 folded into this pass (nf.n == 0: none; the notch_fix kernel follows instead, or there is no list)
-#if CHZ_FWD_BATCH
-  int nbatch; float2* bbuf[4]; float2* bspec[4];
-#endif
 };
 
 // One channel's gather, precomputed on the host from `shift`
@@ -377,11 +330,11 @@ __global__ void fwd_first_real(FirstRealParams p) {
   const int T = p.T;
   const int c0 = tile * T;                       // first packed column of the tile
   const float2* __restrict__ ring2 = reinterpret_cast<const float2*>(p.ring);
-  const long ring2_len = p.ring_len >> 1, start2 = CHZ_BSEL(p.bstart, p.start) >> 1, inner2 = p.inner >> 1;
+  const long ring2_len = p.ring_len >> 1, start2 = p.start >> 1, inner2 = p.inner >> 1;
   const float2* __restrict__ tws = p.tw_sub;
   const float2* __restrict__ twt = p.tw_tile;
   const float2* __restrict__ twc = p.tw_col;
-  float2* __restrict__ gout = CHZ_BSEL(p.bbuf, p.buf);
+  float2* __restrict__ gout = p.buf;
   float2* zl = lds + NA * T + R1 * p.padk;         // second LDS region (see layer 2)
 
   // Epilogue geometry is known up front: one lane owns one PACKED column pc (= two adjacent real
@@ -535,23 +488,11 @@ __global__ void fwd_cols(ColsParams p) {
   const int tid = threadIdx.x;
   const int T = p.T;
   const int tpr = p.inner / T;
-#if CHZ_XCD_AFFINE
-  int row, ct;
-  {
-    const int comp = (((int)blockIdx.x & 7) + 8 - p.xa.rot) & 7, idx = (int)blockIdx.x >> 3;
-    if (comp >= p.xa.ncomp) return;
-    const int r0 = comp * p.xa.Ta - p.xa.shift;
-    const int lo = r0 < 0 ? 0 : r0, hi = r0 + p.xa.Ta < p.rows ? r0 + p.xa.Ta : p.rows;
-    if (idx >= (hi - lo) * tpr) return;
-    row = lo + idx / tpr; ct = idx - (idx / tpr) * tpr;
-  }
-#else
   const int row = blockIdx.x / tpr, ct = blockIdx.x - row * tpr;
-#endif
   const int c0 = ct * T;
   const long base = (long)row * NP * p.inner + c0;
-  const float2* __restrict__ gin = CHZ_BSEL(p.bbuf, p.in);
-  float2* __restrict__ gout = CHZ_BSEL(p.bbuf, p.out);
+  const float2* __restrict__ gin = p.in;
+  float2* __restrict__ gout = p.out;
   const float2* __restrict__ tws = p.tw_sub;
   const float2* __restrict__ twt = p.tw_tile;
   const float2* __restrict__ twc = p.tw_col;
@@ -620,17 +561,10 @@ __global__ void fwd_cols(ColsParams p) {
     CHZ_OUT_DESC(odesc, gout);
     const int o0 = (int)base + k1o * p.inner + to;       // element index into gout: the whole buffer is < 2^31 bytes
     const int ostep = R1 * p.inner;
-#if CHZ_XCD_AFFINE == 1        // plain stores: the lines stay in this XCD's L2 for fwd_rows (a COMPILE-time choice: an untaken run-time
-    static_for<R2>([&](auto k2) {  // branch around a second store flavour cost this pass 6 us, 5.7 -> 12.0)
-      constexpr int K2 = decltype(k2)::value;
-      gout[o0 + K2 * ostep] = cmul(u[K2], full ? wt[K2] : cmul(wt[K2], wc[K2]));
-    });
-#else
     static_for<R2>([&](auto k2) {
       constexpr int K2 = decltype(k2)::value;
       CHZ_STORE(odesc, gout, o0 + K2 * ostep, cmul(u[K2], full ? wt[K2] : cmul(wt[K2], wc[K2])));
     });
-#endif
   }
 }
 
@@ -722,22 +656,13 @@ __global__ void fwd_rows(RowsParams p) {
   HIP_DYNAMIC_SHARED(float2, lds)
   const int tid = threadIdx.x, nthr = blockDim.x;
   const int Ta = p.Ta, ld = p.ld, padg = p.padg;
-#if CHZ_XCD_AFFINE
-  int kb, at;
-  {
-    const int comp = (((int)blockIdx.x & 7) + 8 - p.xa.rot) & 7, idx = (int)blockIdx.x >> 3;
-    if (comp >= p.xa.ncomp || idx >= p.Nb) return;
-    kb = idx; at = comp;
-  }
-#else
   const int kb = blockIdx.x % p.Nb, at = blockIdx.x / p.Nb;
-#endif
   const int a0 = at * Ta - p.ka_shift;           // may be negative for the first (ragged) tile
   const int rowstride = p.Nb * NC;               // all index math below is 32-bit: N < 2^31
   const int gstep = R2 * ld + padg;              // LDS distance between butterfly groups
 
   const float2* __restrict__ tws = p.tw_sub;
-  const float2* __restrict__ gin = CHZ_BSEL(p.bbuf, p.buf) + (long)kb * NC;
+  const float2* __restrict__ gin = p.buf + (long)kb * NC;
   bool nf_owner = false;                           // does this workgroup store a bin of the notch list?  (scalar compares on kernel arguments)
   static_for<CHZ_NOTCH_INLINE>([&](auto ee) { constexpr int E = decltype(ee)::value; nf_owner = nf_owner || (E < p.nf.n && p.nf.wg[E] == (int)blockIdx.x); });
   unsigned nf_mask = 0;                            // ... and which of this thread's second-layer outputs, if any (at most one: rows_notch_fill)
@@ -838,7 +763,7 @@ __global__ void fwd_rows(RowsParams p) {
       const int kk0 = ka + p.Na * x0, kks = p.Na * xs;            // bin index k = kk0 + K2*kks
       const int d0 = x0 * p.lay.pitch + p.lay.off + ka, ds = xs * p.lay.pitch;
       const int m0 = (xrows - 1 - x0) * p.lay.pitch + p.lay.off + (p.Na - ka);
-      float2* __restrict__ sp = CHZ_BSEL(p.bspec, p.spec);
+      float2* __restrict__ sp = p.spec;
       CHZ_OUT_DESC(sdesc, sp);
       // one store per output, no branches: bins up to N/2 go out as they are, the rest conjugated to bin N-k; the
       // self-conjugate rows (ka = 0, Na/2) have no mirror image to write
@@ -2332,17 +2257,6 @@ __global__ void __launch_bounds__(64, CHZ_PLL_WAVES) pll_lanes(DemodParams p) {
         return mixed;
       };
       int n = 0;
-#if CHZ_PLL_UNROLL > 1
-      for (; n + CHZ_PLL_UNROLL <= tn; n += CHZ_PLL_UNROLL) {      // (see demod_lin_lanes: one LDS round trip per group instead of per sample)
-        float2 v[CHZ_PLL_UNROLL];
-#pragma unroll
-        for (int u = 0; u < CHZ_PLL_UNROLL; u++) v[u] = tile[lane * LD + n + u];
-#pragma unroll
-        for (int u = 0; u < CHZ_PLL_UNROLL; u++) v[u] = pll_step(v[u], n + u);
-#pragma unroll
-        for (int u = 0; u < CHZ_PLL_UNROLL; u++) tile[lane * LD + n + u] = v[u];
-      }
-#endif
       for (; n < tn; n++) tile[lane * LD + n] = pll_step(tile[lane * LD + n], n);
     }
     CHZ_WAVE_SYNC();
@@ -2749,7 +2663,6 @@ __global__ void __launch_bounds__(64, CHZ_LIN_WAVES) demod_lin_lanes(DemodParams
         return make_float2(oa, ob);
       };
       int n = 0;
-#if CHZ_LIN_UNROLL > 1
       // the walk is a chain of LDS round trips (read a sample, a few dependent double-precision operations, write it back): CHZ_LIN_UNROLL
       // samples are read together, stepped in order, and written together -- the same operations in the same order, one LDS latency per group
       for (; n + CHZ_LIN_UNROLL <= tn; n += CHZ_LIN_UNROLL) {
@@ -2761,7 +2674,6 @@ __global__ void __launch_bounds__(64, CHZ_LIN_WAVES) demod_lin_lanes(DemodParams
 #pragma unroll
         for (int u = 0; u < CHZ_LIN_UNROLL; u++) tile[lane * LD + n + u] = v[u];
       }
-#endif
       for (; n < tn; n++) tile[lane * LD + n] = final_step(tile[lane * LD + n]);
     }
     CHZ_WAVE_SYNC();
@@ -2906,8 +2818,8 @@ __global__ void __launch_bounds__(64, CHZ_FM_WAVES) demod_fm_lanes(DemodParams p
   if (p0 > 0) p0 /= (p0 + beta * noise);
   // (round 6) split in two: disc_phase() is the long part -- a double-precision atan2 -- and depends on nothing but the sample and its
   // predecessor; disc_commit() is the reference's sequential part (threshold extension, sums, extremes, phase_memory).  The loops below take
-  // CHZ_FM_DISC_UNROLL samples at a time: their atan2 chains are independent and overlap, the commits then run in sample order -- the same
-  // operations on the same values as one sample at a time (bit-identical), the dependent-latency chain per sample a fraction of it.
+  // one sample at a time: computing the phases of 2 / 4 / 8 samples side by side was measured and bought nothing (1.93-1.98 -> 1.99-2.01 /
+  // 2.13-2.17 / 2.49-2.50 ns per channel, profiles/r06_fm_disc_unroll.txt) -- the pass is bound by vector issue, not by the latency of its chains.
   auto disc_phase = [&](const float2 v, const double qr, const double qi) -> double {
     const double br = v.x, bi = v.y;
     const double sr = br * qr + bi * qi, si = bi * qr - br * qi;
@@ -2950,22 +2862,6 @@ __global__ void __launch_bounds__(64, CHZ_FM_WAVES) demod_fm_lanes(DemodParams p
         if (t0 + LIN_TILE < N) fetch_x(t0 + LIN_TILE, var_rows);
         if (need_var) {
           int n = 0;
-#if CHZ_FM_DISC_UNROLL > 1
-          if (pass == 1)
-            for (; n + CHZ_FM_DISC_UNROLL <= tn; n += CHZ_FM_DISC_UNROLL) {
-              float2 v[CHZ_FM_DISC_UNROLL]; double ph[CHZ_FM_DISC_UNROLL];
-#pragma unroll
-              for (int u = 0; u < CHZ_FM_DISC_UNROLL; u++) v[u] = tile[lane * LD + n + u];
-#pragma unroll
-              for (int u = 0; u < CHZ_FM_DISC_UNROLL; u++) ph[u] = u ? disc_phase(v[u], (double)v[u - 1].x, (double)v[u - 1].y) : disc_phase(v[0], pr, pi);
-#pragma unroll
-              for (int u = 0; u < CHZ_FM_DISC_UNROLL; u++) {
-                const double a = (double)demod_cabsf(v[u]);
-                const double dlt = a - avg; var += dlt * dlt;
-                tile[lane * LD + n + u].x = disc_commit(v[u], ph[u]);
-              }
-            }
-#endif
           for (; n < tn; n++) {
             const float2 v = tile[lane * LD + n];
             const double a = (double)demod_cabsf(v);
@@ -3024,17 +2920,6 @@ __global__ void __launch_bounds__(64, CHZ_FM_WAVES) demod_fm_lanes(DemodParams p
       if (t0 + LIN_TILE < N) fetch_x(t0 + LIN_TILE, late_rows);
       if (late) {
         int n = 0;
-#if CHZ_FM_DISC_UNROLL > 1
-        for (; n + CHZ_FM_DISC_UNROLL <= tn; n += CHZ_FM_DISC_UNROLL) {
-          float2 v[CHZ_FM_DISC_UNROLL]; double ph[CHZ_FM_DISC_UNROLL];
-#pragma unroll
-          for (int u = 0; u < CHZ_FM_DISC_UNROLL; u++) v[u] = tile[lane * LD + n + u];
-#pragma unroll
-          for (int u = 0; u < CHZ_FM_DISC_UNROLL; u++) ph[u] = u ? disc_phase(v[u], (double)v[u - 1].x, (double)v[u - 1].y) : disc_phase(v[0], pr, pi);
-#pragma unroll
-          for (int u = 0; u < CHZ_FM_DISC_UNROLL; u++) tile[lane * LD + n + u].x = disc_commit(v[u], ph[u]);
-        }
-#endif
         for (; n < tn; n++) tile[lane * LD + n].x = discriminate(tile[lane * LD + n]);
       }
       CHZ_WAVE_SYNC();
@@ -3111,7 +2996,6 @@ __global__ void __launch_bounds__(64, CHZ_FM_WAVES) demod_fm_lanes(DemodParams p
         return (float)sgn;
       };
       int n = 0;
-#if CHZ_LIN_UNROLL > 1
       for (; n + CHZ_LIN_UNROLL <= tn; n += CHZ_LIN_UNROLL) {       // (see demod_lin_lanes: one LDS round trip per group instead of per sample)
         float v[CHZ_LIN_UNROLL];
 #pragma unroll
@@ -3121,7 +3005,6 @@ __global__ void __launch_bounds__(64, CHZ_FM_WAVES) demod_fm_lanes(DemodParams p
 #pragma unroll
         for (int u = 0; u < CHZ_LIN_UNROLL; u++) tilef[lane * LD + n + u] = v[u];
       }
-#endif
       for (; n < tn; n++) tilef[lane * LD + n] = out_step(tilef[lane * LD + n]);
     }
     CHZ_WAVE_SYNC();

@@ -83,17 +83,6 @@ PY
     timeout 120 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29711 scripts/rccl_sanity.py > "$out/rccl_sanity.txt" 2>&1; echo "rccl rc=$?" >> "$out/rc.txt"
     tail -2 "$out/rccl_sanity.txt"; cat "$out/rc.txt"
     ;;
-  r6h)       # round 6: demod_fm_lanes' discriminator phases 1 / 2 / 4 (shipped) / 8 samples side by side, and 2 wavefronts per SIMD: the FM chain at 1.5 M channels
-    for rep in 1 2; do for v in default fmd1 fmd2 fmd8 fmw2; do
-      L=""; [ $v != default ] && L=$PWD/ka9q-radio_amd/libchz_hip_$v.so
-      CHZ_LIB=$L timeout 200 python scripts/chain_profile.py fm 1500000 >> "$out/fm_$v.jsonl" 2>> "$out/err.txt"
-    done; done
-    for v in default fmd1 fmd2 fmd8 fmw2; do echo "$v: $(cat $out/fm_$v.jsonl | python -c "
-import sys, json
-for ln in sys.stdin:
-    r = json.loads(ln); print(round(r['pipelined_ms_per_block'], 3), round(r['ns_per_channel']['demodulator_and_pcm'], 3), r['pcm_mismatches'], end=' | ')
-")"; done
-    ;;
   r6g)       # round 6: the whole GPU suite + smoke + the driver's command after the options / desc_push / watchdog changes
     timeout 1500 python -m pytest tests -m gpu -q --timeout 600 -x > "$out/gpu_suite.txt" 2>&1; echo "suite rc=$?" >> "$out/rc.txt"
     tail -8 "$out/gpu_suite.txt"
@@ -218,23 +207,6 @@ PY
     SKIP_PMC=0 timeout 900 bash scripts/gpu_profile.sh r05 > "$out/profile.txt" 2>&1
     cat gpurun_out/r05_pmc_forward.json; cat gpurun_out/pmc_r05/retries.txt 2>/dev/null
     ;;
-  r5i)       # round 5: the HBM-streamed forward figure; pll_lanes with 4 samples per LDS round trip (A/B build)
-    $B --quick --detail "$out/quick.json" > "$out/quick.head" 2> "$out/quick.err"; echo "quick rc=$?" >> "$out/rc.txt"
-    python -c "import json; r=json.load(open('$out/quick.json'))['roofline']; print('pipelined', r['pipelined']['forward_us_per_block'], r['pipelined']['frac'], 'streamed', r['streamed'])"
-    NR="--no-crt --no-dropin --no-dropin-paced --no-crt-pcie --no-cpu-baseline --next-rows-modes pll"
-    P4=$PWD/ka9q-radio_amd/libchz_hip_pllu4.so
-    for rep in 1 2; do
-      timeout 200 $B $NR --detail "$out/pll_default_$rep.json" > /dev/null 2>> "$out/err.txt"
-      CHZ_LIB=$P4 timeout 200 $B $NR --detail "$out/pll_u4_$rep.json" > /dev/null 2>> "$out/err.txt"
-    done
-    python - "$out" <<'PY'
-import json, sys, glob, os
-out = sys.argv[1]
-for f in sorted(glob.glob(out + "/pll_*.json")):
-    j = json.load(open(f))
-    print(os.path.basename(f), [(x.get("mode"), round(x.get("pipelined_ms_per_block", 0), 3), x.get("pcm_mismatches"), {k: round(v, 3) for k, v in (x.get("ns_per_channel") or {}).items()}) if "error" not in x else x for x in (j.get("next_rows") or [])])
-PY
-    ;;
   r5h)       # round 5: the C_rt search with the 22 M-channel bank; why the all-streams-masked tree hung (stream callbacks on CU-masked streams?)
     $B --no-dropin --no-dropin-paced --no-crt-pcie --no-cpu-baseline --no-next-rows --detail "$out/crt22.json" > "$out/crt22.head" 2> "$out/crt22.err"; echo "crt22 rc=$?" >> "$out/rc.txt"
     python -c "import json; c=json.load(open('$out/crt22.json'))['c_rt']; print('c_rt', c.get('channels'), c.get('sustained'), c.get('worst_block_ms'), c.get('mean_crossing_channels'), [(p['channels'], p['blocks'], round(p['worst_block_ms'],2), p['sustained']) for p in c.get('probes', [])], c.get('error'))"
@@ -249,27 +221,6 @@ PY
     tail -n 1 "$out/bench_stdout.txt" > "$out/bench_headline.json"; cp gpurun_out/bench_detail.json "$out/bench_detail.json" 2>/dev/null
     wc -c "$out/bench_headline.json"; grep "^bench.py \[" "$out/bench.err" | tail -3
     SKIP_PMC=0 timeout 900 bash scripts/gpu_profile.sh r05 > "$out/profile.txt" 2>&1
-    ;;
-  r5f)       # round 5, fifth call: the driver's command with the demodulator stream alone on its own queue (bounded: r5d's run with EVERY stream masked hung in one of the legs), then A/Bs of the chain
-    timeout 420 $B > "$out/bench_stdout.txt" 2> "$out/bench.err"; echo "bench rc=$?" >> "$out/rc.txt"
-    tail -n 1 "$out/bench_stdout.txt" > "$out/bench_headline.json"; cp gpurun_out/bench_detail.json "$out/bench_detail.json" 2>/dev/null
-    grep "^bench.py \[" "$out/bench.err" | tail -20
-    NR="--no-crt --no-dropin --no-dropin-paced --no-crt-pcie --no-cpu-baseline --next-rows-modes linear"
-    run_chain() { tag=$1; shift; env "$@" timeout 200 $B $NR --detail "$out/chain_$tag.json" > /dev/null 2>> "$out/err.txt"; }
-    run_chain q0 CHZ_OWN_QUEUES=0
-    run_chain q1 CHZ_OWN_QUEUES=1
-    run_chain q2 CHZ_OWN_QUEUES=2
-    run_chain linu4 CHZ_LIB=$PWD/ka9q-radio_amd/libchz_hip_linu4.so
-    run_chain linu8 CHZ_LIB=$PWD/ka9q-radio_amd/libchz_hip_linu8.so
-    run_chain q1b CHZ_OWN_QUEUES=1
-    python - "$out" <<'PY'
-import json, sys, glob, os
-out = sys.argv[1]
-for f in sorted(glob.glob(out + "/chain_*.json")):
-    j = json.load(open(f))
-    print(os.path.basename(f), [(x.get("mode"), round(x.get("pipelined_ms_per_block", 0), 3), x.get("pcm_mismatches"), {k: round(v, 3) for k, v in (x.get("ns_per_channel") or {}).items()}) if "error" not in x else x for x in (j.get("next_rows") or [])], "headline us/step", round(j["ms_per_step"] * 1e3, 2))
-PY
-    wc -c "$out/bench_headline.json"; head -c 1500 "$out/bench_headline.json"
     ;;
   r5d)       # round 5, fourth call: demod_lin_lanes at 4 wavefronts per SIMD (A/B build), then the whole GPU suite on the tree with own hardware queues
     NR="--no-crt --no-dropin --no-dropin-paced --no-crt-pcie --no-cpu-baseline --next-rows-modes linear"
@@ -296,70 +247,6 @@ PY
     wc -c "$out/bench_headline.json"; cat "$out/bench_headline.json"
     SKIP_PMC=0 timeout 1500 bash scripts/gpu_profile.sh r05 > "$out/profile.txt" 2>&1
     ;;
-  r5c)       # round 5, third call: is the CU-mask gain the partition or the hardware-queue assignment?  + the batched passes, fixed build
-    NR="--no-crt --no-dropin --no-dropin-paced --no-crt-pcie --no-cpu-baseline --next-rows-modes linear"
-    run_chain() { tag=$1; shift; env "$@" $B $NR --detail "$out/chain_$tag.json" > "$out/chain_$tag.head" 2>> "$out/err.txt"; }
-    run_chain base1 X=1
-    run_chain q8_1 GPU_MAX_HW_QUEUES=8
-    run_chain cus256_1 CHZ_TAIL_CUS=256
-    run_chain cus96_1 CHZ_TAIL_CUS=96
-    run_chain cus128_1 CHZ_TAIL_CUS=128
-    run_chain base2 X=1
-    run_chain q8_2 GPU_MAX_HW_QUEUES=8
-    run_chain cus256_2 CHZ_TAIL_CUS=256
-    run_chain cus96_2 CHZ_TAIL_CUS=96
-    run_chain cus96q8 CHZ_TAIL_CUS=96 GPU_MAX_HW_QUEUES=8
-    LIBB=$PWD/ka9q-radio_amd/libchz_hip_batch.so
-    for rep in 1 2; do
-      BENCH_NO_NOTCH=1 $B --quick --detail "$out/fwd_base_$rep.json" > /dev/null 2>> "$out/err.txt"
-      BENCH_NO_NOTCH=1 GPU_MAX_HW_QUEUES=8 $B --quick --detail "$out/fwd_baseq8_$rep.json" > /dev/null 2>> "$out/err.txt"
-      BENCH_NO_NOTCH=1 CHZ_LIB=$LIBB $B --quick --detail "$out/fwd_batchlib_n0_$rep.json" > /dev/null 2>> "$out/err.txt"
-      BENCH_NO_NOTCH=1 CHZ_LIB=$LIBB CHZ_FWD_BATCH_N=2 $B --quick --detail "$out/fwd_batch2_$rep.json" > /dev/null 2>> "$out/err.txt"
-      BENCH_NO_NOTCH=1 CHZ_LIB=$LIBB CHZ_FWD_BATCH_N=4 $B --quick --detail "$out/fwd_batch4_$rep.json" > /dev/null 2>> "$out/err.txt"
-    done
-    for n in 2 4; do CHZ_LIB=$LIBB CHZ_FWD_BATCH_N=$n timeout 300 python scripts/batch_check.py >> "$out/batch_parity.txt" 2>&1; done
-    python - "$out" <<'PY'
-import json, sys, glob, os
-out = sys.argv[1]
-for f in sorted(glob.glob(out + "/chain_*.json")):
-    j = json.load(open(f))
-    print(os.path.basename(f), [(x.get("mode"), round(x.get("pipelined_ms_per_block", 0), 3), x.get("pcm_mismatches"), {k: round(v, 3) for k, v in (x.get("ns_per_channel") or {}).items()}) if "error" not in x else x for x in (j.get("next_rows") or [])], "headline us/step", round(j["ms_per_step"] * 1e3, 2))
-for f in sorted(glob.glob(out + "/fwd_*.json")):
-    j = json.load(open(f)); r = j["roofline"]
-    print(os.path.basename(f), "ms_per_step", round(j["ms_per_step"] * 1e3, 2), "fwd_pipelined_us", round(r["pipelined"]["forward_us_per_block"], 2), "frac", round(r["pipelined"]["frac"], 4))
-PY
-    cat "$out/batch_parity.txt"
-    ;;
-  r5b)       # round 5, second call: profiles of the shipped kernels (folded notch), the CU-mask and batched-pass experiments, the packed PCM store
-    NR="--no-crt --no-dropin --no-dropin-paced --no-crt-pcie --no-cpu-baseline --next-rows-modes linear"
-    for cus in 0 32 64 96; do      # (0 = unset: plain streams)
-      if [ $cus = 0 ]; then $B $NR --detail "$out/chain_cus0.json" > "$out/chain_cus0.head" 2>> "$out/err.txt"
-      else CHZ_TAIL_CUS=$cus $B $NR --detail "$out/chain_cus$cus.json" > "$out/chain_cus$cus.head" 2>> "$out/err.txt"; fi
-    done
-    $B --no-crt --no-dropin --no-dropin-paced --no-crt-pcie --no-cpu-baseline --next-rows-modes pll,fm --detail "$out/chain_pllfm.json" > "$out/chain_pllfm.head" 2>> "$out/err.txt"
-    LIBB=$PWD/ka9q-radio_amd/libchz_hip_batch.so
-    for rep in 1 2; do
-      BENCH_NO_NOTCH=1 $B --quick --detail "$out/fwd_base_$rep.json" > /dev/null 2>> "$out/err.txt"
-      BENCH_NO_NOTCH=1 CHZ_LIB=$LIBB $B --quick --detail "$out/fwd_batchlib_n0_$rep.json" > /dev/null 2>> "$out/err.txt"
-      BENCH_NO_NOTCH=1 CHZ_LIB=$LIBB CHZ_FWD_BATCH_N=2 $B --quick --detail "$out/fwd_batch2_$rep.json" > /dev/null 2>> "$out/err.txt"
-      BENCH_NO_NOTCH=1 CHZ_LIB=$LIBB CHZ_FWD_BATCH_N=4 $B --quick --detail "$out/fwd_batch4_$rep.json" > /dev/null 2>> "$out/err.txt"
-    done
-    for n in 2 4; do CHZ_LIB=$LIBB CHZ_FWD_BATCH_N=$n timeout 300 python scripts/batch_check.py >> "$out/batch_parity.txt" 2>&1; done
-    python - "$out" <<'PY'
-import json, sys, glob, os
-out = sys.argv[1]
-for f in sorted(glob.glob(out + "/chain_*.json")):
-    j = json.load(open(f))
-    print(os.path.basename(f), [(x.get("mode"), round(x.get("pipelined_ms_per_block", 0), 3), x.get("pcm_mismatches"), {k: round(v, 3) for k, v in (x.get("ns_per_channel") or {}).items()}) if "error" not in x else x for x in (j.get("next_rows") or [])])
-for f in sorted(glob.glob(out + "/fwd_*.json")):
-    j = json.load(open(f)); r = j["roofline"]
-    print(os.path.basename(f), "ms_per_step", round(j["ms_per_step"] * 1e3, 2), "fwd_pipelined_us", round(r["pipelined"]["forward_us_per_block"], 2), "frac", round(r["pipelined"]["frac"], 4))
-PY
-    timeout 600 python -m pytest tests/test_dropin.py tests/test_gpu_scale.py -m gpu -q --timeout 400 -k "clique or two_shards or end_to_end" > "$out/newtests.txt" 2>&1; echo "newtests rc=$?" >> "$out/rc.txt"
-    tail -3 "$out/newtests.txt"
-    SKIP_PMC=0 timeout 1500 bash scripts/gpu_profile.sh r05 > "$out/profile.txt" 2>&1
-    tail -3 "$out/batch_parity.txt"
-    ;;
   r5a)       # round 5, first call: the drop-in's cold start + sharding on hardware, the compact bench line, the C_rt search
     timeout 900 python -m pytest tests/test_dropin.py -m gpu -q --timeout 600 > "$out/dropin.txt" 2>&1; echo "dropin rc=$?" >> "$out/rc.txt"
     tail -5 "$out/dropin.txt"
@@ -385,38 +272,6 @@ PY
     nproc > "$out/host.txt"; cat /sys/fs/cgroup/cpu.max >> "$out/host.txt" 2>&1; cat /sys/fs/cgroup/cpu.stat >> "$out/host.txt" 2>&1; uptime >> "$out/host.txt"
     $B --no-crt --no-next-rows --no-crt-pcie --no-cpu-baseline > "$out/bench_paced.json" 2> "$out/bench_paced.err"; echo "bench rc=$?" >> "$out/rc.txt"
     cat /sys/fs/cgroup/cpu.stat >> "$out/host.txt" 2>&1
-    ;;
-  xcd)       # round 4 experiment: XCD-affine fwd_cols -> fwd_rows hand-over (build variants libchz_hip_xcd{1,2}.so), timing + L2 counters
-    X1="CHZ_LIB=$PWD/ka9q-radio_amd/libchz_hip_xcd1.so CHZ_NOTCH_FOLD=0"      # affine placement + plain hand-over stores
-    X2="CHZ_LIB=$PWD/ka9q-radio_amd/libchz_hip_xcd2.so CHZ_NOTCH_FOLD=0"      # affine placement, write-through stores kept
-    env $X1 timeout 600 python -m pytest tests/test_gpu_parity.py -m gpu -q --timeout 300 -k "forward_matches_oracle and (2592000 or 1296000)" > "$out/parity_affine.txt" 2>&1; echo "parity rc=$?" >> "$out/rc.txt"
-    for rep in 1 2; do
-      CHZ_NOTCH_FOLD=0 $B --quick > "$out/base_$rep.json" 2>> "$out/err.txt"
-      env $X1 $B --quick > "$out/affine_plain_$rep.json" 2>> "$out/err.txt"
-      env $X2 $B --quick > "$out/affine_wt_$rep.json" 2>> "$out/err.txt"
-    done
-    for lanes in 1 2; do
-      CHZ_NOTCH_FOLD=0 CHZ_STREAMS=$lanes $B --quick > "$out/base_lanes$lanes.json" 2>> "$out/err.txt"
-      env $X1 CHZ_STREAMS=$lanes $B --quick > "$out/affine_plain_lanes$lanes.json" 2>> "$out/err.txt"
-    done
-    R=$PWD; cd /tmp
-    for v in base affine; do
-      E="CHZ_NOTCH_FOLD=0 CHZ_NOTCH_ORDER=event"; [ $v = affine ] && E="$X1 CHZ_NOTCH_ORDER=event"
-      for c in "TCC_HIT_sum TCC_MISS_sum" "FETCH_SIZE" "WRITE_SIZE"; do
-        n=$(echo $c | cut -d' ' -f1)
-        env $E timeout 240 rocprofv3 --pmc $c -f csv -d $R/$out/pmc_${v}_$n -o $n -- python $R/bench.py --steps 160 --warmup 16 --min-seconds 0.05 --quick > $R/$out/pmc_${v}_$n.log 2>&1
-      done
-    done
-    cd $R
-    python scripts/rocprof_summary.py $out/pmc_base_TCC_HIT_sum $out/pmc_affine_TCC_HIT_sum $out/pmc_base_FETCH_SIZE $out/pmc_affine_FETCH_SIZE $out/pmc_base_WRITE_SIZE $out/pmc_affine_WRITE_SIZE > "$out/pmc_summary.txt" 2>&1
-    rm -rf $out/pmc_*/ 2>/dev/null
-    ;;
-  agc)       # round 4: L2 hand-over microbenchmark; the AGC's first look in chan_ifft's epilogue, A/B at 1.5 M channels; demodulator tests
-    ./scripts/micro/xcd_l2_handover.bin > "$out/xcd_l2_handover.txt" 2>&1
-    NR="--no-crt --no-dropin --no-dropin-paced --no-crt-pcie --no-cpu-baseline"
-    $B $NR > "$out/next_rows_peak.json" 2> "$out/err.txt"
-    CHZ_AGC_PEAK=0 $B $NR > "$out/next_rows_nopeak.json" 2>> "$out/err.txt"
-    timeout 1200 python -m pytest tests/test_gpu_scale.py tests/test_gpu_pipeline.py tests/test_golden.py -m gpu -x -q --timeout 600 -k "demod or scale or 70001 or golden or coherent or fm" > "$out/demod_tests.txt" 2>&1; echo "tests rc=$?" >> "$out/rc.txt"
     ;;
   profile)   # the round's profile: kernel trace (4 streams and 1), PMC passes, summaries for profiles/
     GRAFT_REPO_ROOT=$PWD bash scripts/gpu_profile.sh r04 > "$out/profile.txt" 2>&1; echo "profile rc=$?" >> "$out/rc.txt"
