@@ -388,6 +388,45 @@ int chz_mini_set_response(chz_mini *m, int inst, const float *resp);            
 int chz_mini_execute(chz_mini *m, int n, const int *inst, const float *const *win, const int *shift, const unsigned char *isb,
                      float *const *out);
 
+/* ---- Welch power spectra of the raw input: radiod's wideband spectrum analyser (wideband_poll(), src/spectrum.c:308-522) on the
+ * samples the engine's input ring holds (float REAL, float COMPLEX or the int16 of chz_input_write_i16).  A bank holds `capacity`
+ * analysers sharing one fft_n (= lrint(samprate / rbw): any length from 8 to 2^20 points; one with a prime factor above 13 runs as
+ * chirp-z and needs 2^k >= 2 fft_n - 1 to fit as well), each with its own window, bin shift, bin count, averaging count and
+ * overlap.  Per analyser and poll: fft_avg segments of fft_n samples, hop = lrint(fft_n (1 - overlap)), the first one starting
+ * adjust = lrint(fft_n (1 + (fft_avg - 1)(1 - overlap))) samples in front of the end of the window -- a REAL master's segments
+ * then walk forwards, a COMPLEX master's backwards, as the reference's two branches do (:366,:407 / :424,:491) -- each times the
+ * window, transformed, and gain |X[binp]|^2 added bin by bin in iteration order in the reference's types (float bins, double
+ * sums; gain = 2 or 1 / (fft_avg fft_n^2), :373,:431).  The bin walks are :396-406 (real: DC and the positive frequencies, then
+ * the wrap to the negative output half; a negative shift inverts the spectrum by the sign flip of :381-391) and :477-488
+ * (complex: signed offsets).  Bins outside the front end's coverage stay zero.  The same input gives the same bits, whatever else
+ * is polled in the same call.  Byte encoding and window generation stay with the caller. */
+/* returns a bank id; refuses (with a message) an fft_n no transform covers or longer than the input ring */
+int chz_welch_create(chz_engine *e, int fft_n, int capacity, int max_bins, int max_avg);
+int chz_welch_destroy(chz_engine *e, int bank);
+/* fft_n floats, as generate_window() leaves them in chan->spectrum.window (zeros until set) */
+int chz_welch_set_window(chz_engine *e, int bank, int slot, const float *window);
+/* shift = chan->filter.bin_shift scaled to fft_n (:347).  fft_avg is limited to the data on hand by the reference's formula with
+ * the DEVICE ring's length: floor(1 + (ring_samples / fft_n - 1) / (1 - overlap)), integer quotient (:359-361); the effective
+ * value is returned (< 0: error -- a value that is still above the bank's max_avg among them). */
+int chz_welch_configure(chz_engine *e, int bank, int slot, int shift, int bin_count, int fft_avg, double overlap);
+/* one launch pair for analysers slots[0..nslots) (NULL: 0..nslots-1), on a stream of the polls' own: ordered behind every
+ * chz_input_write* issued before it, in no lane's chain.  end_sample is the ring position (samples; job * L is where block job's
+ * new samples start, as for chz_forward; taken modulo the ring length) just past the newest sample of the window; < 0 = the
+ * write position, i.e. everything written so far.  A later chz_input_write* that would overwrite samples an unfinished poll
+ * still reads waits for that poll; other writes do not.  Both orderings cover chz_input_write* only: a run of
+ * chz_run_blocks_sharded in mode 2 fills the ring of every rank on the communicator's stream, outside them -- poll such an engine
+ * between those runs (after chz_sync), with an explicit end_sample on the ranks other than the root, whose write position does not move.
+ * Option welch_packed (chz_set_option, read by chz_welch_create): 1 (default) = a REAL master's even fft_n runs as a half-length packed
+ * transform with a Hermitian split where the bins are read, 0 = as a full-length complex transform. */
+int chz_welch_poll(chz_engine *e, int bank, int nslots, const int *slots, long long end_sample);
+/* bins: n rows of max_bins floats (the first bin_count of a row are the analyser's bin_data, FFT order as the reference leaves
+ * them); minmax: n pairs (min_power, max_power) over those bins as :498-507 leave them, from which the caller derives base and step
+ * (:508-520).  Either may be NULL.  Synchronous / asynchronous in the polls' stream: completion of the latter is observed through
+ * chz_host_callback(e, CHZ_SLOT_WELCH, ..) or chz_slot_sync(e, CHZ_SLOT_WELCH) (or chz_sync). */
+#define CHZ_SLOT_WELCH (-2)
+int chz_welch_read(chz_engine *e, int bank, int slot0, int n, float *bins, double *minmax);
+int chz_welch_read_async(chz_engine *e, int bank, int slot0, int n, float *bins, double *minmax);
+
 /* host-side helper exposed for tests: the closed-form gather descriptor
  * {t0,cnt,src0,dir,conj,wrap} that restates src/filter.c:728-911 */
 int chz_gather_descriptor(int in_type, int master_bins, int P, int shift, int out6[6]);

@@ -43,6 +43,15 @@ int filter_hip_devices(struct filter_in const *master, int *counts, int max);
  *     static void hw_off(void) { if (Frontend.shutdown) Frontend.shutdown(&Frontend); }   ...   filter_hip_set_exit_hook(hw_off);
  * Called once, from the failing thread, before stdio is flushed and _exit(EX_SOFTWARE).  NULL removes it. */
 void filter_hip_set_exit_hook(void (*hook)(void));
+/* The wideband spectrum analyser on the device: what wideband_poll() (src/spectrum.c:308-522) computes from the raw A/D ring on the
+ * host -- fft_avg overlapping windowed segments of fft_n samples, transformed, |X|^2 of bin_count bins around `shift` summed into
+ * bin_data[] in the reference's bin order -- computed from the newest samples the master's DEVICE ring holds (with KA9Q_HIP_DEVICES: the
+ * first device's).  window = chan->spectrum.window (fft_n floats); minmax (may be NULL) receives min_power / max_power of :498-507.
+ * Synchronous.  Returns the effective fft_avg (limited to the data on hand as :359-361 limit it), -1 when the master has no device ring
+ * (a small inline master) or on bad arguments.  (Named outside this header's other prefix on purpose: the set of names carrying that
+ * prefix is pinned by the exported-symbol test.) */
+int ka9q_hip_spectrum(struct filter_in *master, int fft_n, const float *window, int shift, int bin_count, int fft_avg, double overlap,
+                      float *bin_data, double minmax[2]);
 #ifdef __cplusplus
 }
 #endif

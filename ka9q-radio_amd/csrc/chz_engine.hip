@@ -201,6 +201,7 @@ struct NotchTurn {
 };
 
 #define CHZ_NOTCH_EVENTS 8
+struct WelchBank;                   // chz_welch.inc
 
 struct chz_engine {
   int L = 0, M = 0, N = 0, in_type = 0, bins = 0, per = 1, device = 0, ring_blocks = 0;
@@ -263,6 +264,13 @@ struct chz_engine {
   NotchOwn* notch_own = nullptr;                        // device: who stores each listed bin inside fwd_rows
   RowsNotch notch_fold{};                               // n > 0: the list rides inside fwd_rows (short lists, directly planned masters; env CHZ_NOTCH_FOLD=0 keeps the kernel)
   std::vector<Bank> banks;
+  // Welch power spectra of the raw input (chz_welch_*, chz_welch.inc): polls run on a stream of their own, behind the input writes issued
+  // before them; an input write that would overwrite samples an unfinished poll still reads waits for that poll (welch_guard)
+  std::vector<WelchBank*> welch;
+  hipStream_t welch_s = nullptr;
+  hipEvent_t welch_in = nullptr, welch_done = nullptr;   // on the input stream in front of a poll / on the poll's stream behind it
+  bool welch_busy = false;                                // a poll may still be reading ring samples [welch_lo, welch_lo + welch_len)
+  long long welch_lo = 0, welch_len = 0;
   hipGraphExec_t graph = nullptr; unsigned graph_job0 = 0; int graph_blocks = 0;
   int capture_blocks = 0;           // blocks of the capture in progress (the last one moves the ticket base on)
   int graph_min_blocks = 32;        // env CHZ_GRAPH_BLOCKS: a replay covers at least this many blocks (drained once per replay)
@@ -282,6 +290,21 @@ template <class T> static int upload(T** dst, const std::vector<f2>& v) {
   if (v.empty()) return 0;
   HIPOK(hipMalloc((void**)dst, v.size() * sizeof(f2)));
   HIPOK(hipMemcpy(*dst, v.data(), v.size() * sizeof(f2), hipMemcpyHostToDevice));
+  return 0;
+}
+
+static void welch_free_all(chz_engine* e);      // chz_welch.inc
+// in front of an input write of n samples at ring position pos: the write waits for an unfinished poll that reads any of them
+static int welch_guard(chz_engine* e, long long pos, long long n) {
+  if (!e->welch_busy || n <= 0) return 0;
+  const long long R = e->ring_len / e->per;
+  { chz_exit::Scope xs; if (!xs.ok) return 0;
+    if (hipEventQuery(e->welch_done) == hipSuccess) { e->welch_busy = false; return 0; }
+    (void)hipGetLastError(); }
+  const long long d1 = ((pos - e->welch_lo) % R + R) % R, d2 = ((e->welch_lo - pos) % R + R) % R;
+  if (!(d1 < e->welch_len || d2 < n)) return 0;
+  HIPOK(hipStreamWaitEvent(e->stream, e->welch_done, 0));
+  e->welch_busy = false;        // every later write is queued behind this one
   return 0;
 }
 
@@ -354,6 +377,7 @@ struct ChzOptions {
   double notch_wait_ms = 3000.0;  // budget of a device-side ticket wait
   int fault_ticket_skew = 0;  // fault injection for the hosts' recovery paths: the host's tickets start this far ahead of the device's counter ...
   int allow_fault_injection = 0;  // ... only with this set as well
+  int welch_packed = 1;       // chz_welch_create: real front end, even fft_n -- 1: half-length packed transform + Hermitian split (measured faster at every size), 0: full-length complex transform
   char launch_id[64] = {0};   // chz_comm_create_file: the id of this launch (ranks of another launch's rendezvous file are refused)
 };
 static ChzOptions g_opt;
@@ -376,6 +400,7 @@ extern "C" int chz_set_option(const char* name, const char* value) {
   else if (n == "notch_wait_ms") g_opt.notch_wait_ms = (d || !(atof(value) > 0)) ? def.notch_wait_ms : atof(value);
   else if (n == "fault_ticket_skew") g_opt.fault_ticket_skew = d ? 0 : iv;
   else if (n == "allow_fault_injection") g_opt.allow_fault_injection = d ? 0 : (value[0] == '1');
+  else if (n == "welch_packed") g_opt.welch_packed = d ? def.welch_packed : (iv != 0);
   else if (n == "launch_id") snprintf(g_opt.launch_id, sizeof g_opt.launch_id, "%s", d ? "" : value);
   else return fail(-1, "unknown option '%s'", name);
   return 0;
@@ -550,7 +575,9 @@ void chz_engine_destroy(chz_engine* e) {
   if (e->upload) hipStreamSynchronize(e->upload);
   if (e->tail) hipStreamSynchronize(e->tail);
   if (e->pcmcopy) hipStreamSynchronize(e->pcmcopy);
+  if (e->welch_s) hipStreamSynchronize(e->welch_s);
   drop_graph(e);
+  welch_free_all(e);
   for (int i = 0; i < e->nlanes; i++) {
     hipFree(e->lanes[i].buf);
     if (i > 0 && e->lanes[i].s) hipStreamDestroy(e->lanes[i].s);
@@ -581,6 +608,9 @@ void chz_engine_destroy(chz_engine* e) {
   if (e->upload) hipStreamDestroy(e->upload);
   if (e->tail) hipStreamDestroy(e->tail);
   if (e->pcmcopy) hipStreamDestroy(e->pcmcopy);
+  if (e->welch_s) hipStreamDestroy(e->welch_s);
+  if (e->welch_in) hipEventDestroy(e->welch_in);
+  if (e->welch_done) hipEventDestroy(e->welch_done);
   if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
   delete e;
 }
@@ -625,6 +655,7 @@ static int sync_all(chz_engine* e) {
   for (int i = 0; i < e->nlanes; i++) HIPOK(hipStreamSynchronize(e->lanes[i].s));
   if (e->tail) HIPOK(hipStreamSynchronize(e->tail));
   if (e->pcmcopy) HIPOK(hipStreamSynchronize(e->pcmcopy));
+  if (e->welch_s) { HIPOK(hipStreamSynchronize(e->welch_s)); e->welch_busy = false; }
   // nothing is travelling any more: the demodulator launches that follow (a graph capture among them: an eagerly recorded event is no
   // business of a capture) need not wait for the copy stream's last read of their slot
   for (auto& b : e->banks) for (int s = 0; s < CHZ_ND; s++) b.pcm_copying[s] = false;
@@ -645,6 +676,7 @@ static int ring_write(chz_engine* e, const float* src, long n, hipMemcpyKind kin
   if (e->ring16) return fail(-1, "int16 and float input cannot be mixed on one engine");
   const long nf = n * e->per;
   if (nf < 0 || nf > e->ring_len) return fail(-1, "write of %ld samples does not fit the ring", n);
+  { int r = welch_guard(e, e->wpos / e->per, n); if (r) return r; }
   const long first = (e->wpos + nf <= e->ring_len) ? nf : e->ring_len - e->wpos;
   if (first > 0) HIPOK(hipMemcpyAsync(e->ring + e->wpos, src, sizeof(float) * (size_t)first, kind, e->stream));
   if (nf > first) HIPOK(hipMemcpyAsync(e->ring, src + first, sizeof(float) * (size_t)(nf - first), kind, e->stream));
@@ -682,6 +714,7 @@ static int ring16_write(chz_engine* e, const short* src, long n, float scale, in
   }
   if (scale != e->scale16 || (randomize != 0) != (e->derand != 0)) drop_graph(e);   // baked into captured launches
   e->scale16 = scale; e->derand = randomize != 0;
+  { int r = welch_guard(e, e->wpos, n); if (r) return r; }
   const long first = (e->wpos + n <= e->ring_len) ? n : e->ring_len - e->wpos;
   if (first > 0) HIPOK(hipMemcpyAsync(e->ring16 + e->wpos, src, sizeof(short) * (size_t)first, kind, e->stream));
   if (n > first) HIPOK(hipMemcpyAsync(e->ring16, src + first, sizeof(short) * (size_t)(n - first), kind, e->stream));
@@ -1884,12 +1917,14 @@ int chz_spectrum_read_async(chz_engine* e, int slot, float* host) {
 }
 int chz_host_callback(chz_engine* e, int slot, void (*fn)(void*), void* arg) {
   if (e) { chz_exit::Scope _xd; if (_xd.ok) (void)hipSetDevice(e->device); }       // several engines of one process may sit on different devices (KA9Q_HIP_DEVICES)
+  if (e && fn && slot == CHZ_SLOT_WELCH && e->welch_s) { HIPOK(hipLaunchHostFunc(e->welch_s, fn, arg)); return 0; }
   if (!e || !fn || slot < 0 || slot >= CHZ_ND) return fail(-1, "bad argument");
   HIPOK(hipLaunchHostFunc(slot_stream(e, slot), fn, arg));
   return 0;
 }
 int chz_slot_sync(chz_engine* e, int slot) {
   if (e) { chz_exit::Scope _xd; if (_xd.ok) (void)hipSetDevice(e->device); }       // several engines of one process may sit on different devices (KA9Q_HIP_DEVICES)
+  if (e && slot == CHZ_SLOT_WELCH && e->welch_s) { HIPOK(hipStreamSynchronize(e->welch_s)); return 0; }
   if (!e || slot < 0 || slot >= CHZ_ND) return fail(-1, "bad argument");
   HIPOK(hipStreamSynchronize(slot_stream(e, slot)));
   return 0;
@@ -2137,3 +2172,4 @@ int chz_run_blocks(chz_engine* e, unsigned job0, int nblocks, int mode, int inst
 
 #include "chz_comm.inc"
 #include "chz_mini.inc"
+#include "chz_welch.inc"

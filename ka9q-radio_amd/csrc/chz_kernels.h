@@ -3556,4 +3556,178 @@ __global__ void __launch_bounds__(1024) chan_any(AnyParams q) {
   }
 }
 
+// ------------------------------------------------------------------------------
+// Welch power spectra of the raw input: radiod's wideband spectrum analyser (wideband_poll(), src/spectrum.c:308-522) on the
+// samples the engine's input ring already holds.  A bank of analysers shares one fft_n; a poll is two launches:
+//   welch_seg  one workgroup per (analyser, segment): fft_n ring samples with wrap-around (float REAL, float2 COMPLEX or the raw
+//              int16 of chz_input_write_i16, converted as fwd_first_real converts them) x the analyser's window, the sign flip of
+//              a real front end's negative shift (:381-391), the forward fft_n-point transform through the Stockham stages of
+//              mini_fft (LDS, or global scratch beyond CHZ_ANY_LDS_P points; Bluestein for a prime factor above 13, as chan_any),
+//              then |X[binp]|^2 of the requested bins in the reference's walk (:396-406 real, :477-488 complex) into a
+//              per-segment row.  Bins outside the front end's coverage are zero, a non-finite power counts as zero (:404,:486).
+//   welch_sum  per analyser: the segments added IN ITERATION ORDER in the reference's types, bin = (float)((double)bin + gain * p)
+//              (:405,:487), and the smallest / largest bin (:498-507).  No atomics: the same input gives the same bits.
+// A real front end's segment s starts at end - adjust + s * hop (:366,:407); a complex one's at end - adjust - s * hop (the
+// reference walks backwards from its first segment, :424,:491).
+// Bluestein here is chan_any's identity read the other way round: |F(x)_k| = |B(conj x)_k|, so with a = conj(x) w, b = conj(w) the
+// table F(b) of build_chan_geom serves unchanged, and the closing chirp (modulus 1) is not needed for a power.
+// ------------------------------------------------------------------------------
+struct WelchSlot {
+  int shift, bin_count, fft_avg, hop;   // fft_avg == 0: not configured
+  long long adjust;                     // samples between the first segment's start and the end of the window
+  double gain;                          // 2 or 1 / (fft_avg * fft_n^2)  (:373,:431)
+};
+struct WelchParams {
+  const float* ring; const short* ring16; float scale16; int derand;
+  long long ring_samples, end;          // ring length and (end of the window) mod ring length, in samples
+  int complex_in;
+  const WelchSlot* slot;                // [cap]
+  const int* list;                      // [nslots] the analysers of this poll
+  int nslots, segs;                     // segs: the largest fft_avg among them (grid = nslots * segs work items)
+  const float* window;                  // [cap][fft_n]
+  float* part;                          // [cap][max_avg][max_bins]
+  float* bins;                          // [cap][max_bins]
+  double* minmax;                       // [cap][2]
+  int max_bins, max_avg, fft_n;
+  MiniParams m;                         // m.N = fft_n, or Bluestein's M with m.tw = W_M [M], chirp [fft_n], F(b) [M]
+  float2* scratch;                      // BIG: [gridDim.x][2][m.N]
+  // packed (real input, even fft_n without a prime factor above 13): adjacent samples travel as one complex value through an
+  // fft_n/2-point transform (m.N = fft_n/2) and bin k is recovered where it is read, X_k = (Z_k + conj Z_{H-k})/2 - i/2 W^k (Z_k - conj Z_{H-k})
+  int packed;
+  const float2* tw_split;               // [fft_n] e^{-2 pi i k / fft_n}
+};
+
+template <bool BIG>
+__global__ void __launch_bounds__(1024) welch_seg(WelchParams q) {
+  HIP_DYNAMIC_SHARED(float2, lds)
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int P = q.fft_n, LB = q.m.N;
+  float2* A = BIG ? q.scratch + (size_t)blockIdx.x * 2 * (size_t)LB : lds;
+  float2* B = A + LB;
+  const long long R = q.ring_samples;
+  const int items = q.nslots * q.segs;
+  for (int item = (int)blockIdx.x; item < items; item += (int)gridDim.x) {       // (everything below is workgroup-uniform control flow)
+    const int si = item / q.segs, seg = item - si * q.segs;
+    const int sl = q.list[si];
+    const WelchSlot d = q.slot[sl];
+    if (seg >= d.fft_avg) continue;
+    long long s0 = q.end - d.adjust + (q.complex_in ? -(long long)seg : (long long)seg) * (long long)d.hop;
+    s0 %= R; if (s0 < 0) s0 += R;
+    const float* __restrict__ win = q.window + (size_t)sl * P;
+    const bool flip = !q.complex_in && d.shift < 0;
+    if (q.packed) {
+      for (int i = tid; i < LB; i += nthr) {                                   // LB = P/2; the pair (2i, 2i+1)
+        float x[2];
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+          long long idx = s0 + 2 * i + u; if (idx >= R) idx -= R;
+          if (q.ring16 != nullptr) {
+            int a = (int)q.ring16[idx];
+            if (q.derand) { a ^= -(a & 1) & 0xfffe; a = (int)(short)a; }
+            float f = (float)a * q.scale16;
+            CHZ_ROUNDED_F32(f);
+            x[u] = f;
+          } else x[u] = q.ring[idx];
+          x[u] *= win[2 * i + u];
+        }
+        if (flip) x[1] = -x[1];                                                 // :385-388 (fft_n is even here)
+        A[i] = make_float2(x[0], x[1]);
+      }
+    } else
+    for (int i = tid; i < LB; i += nthr) {
+      float2 v = make_float2(0.f, 0.f);
+      if (i < P) {
+        long long idx = s0 + i; if (idx >= R) idx -= R;                        // fft_n <= R
+        const float w = win[i];
+        if (q.complex_in) { const float2 x = reinterpret_cast<const float2*>(q.ring)[idx]; v = make_float2(w * x.x, w * x.y); }
+        else {
+          float x;
+          if (q.ring16 != nullptr) {
+            int a = (int)q.ring16[idx];
+            if (q.derand) { a ^= -(a & 1) & 0xfffe; a = (int)(short)a; }
+            x = (float)a * q.scale16;                                           // the rounded product, as convert() stores it
+            CHZ_ROUNDED_F32(x);
+          } else x = q.ring[idx];
+          float y = w * x;
+          if (flip) { if (i & 1) y = -y; if ((P & 1) && i == P - 1) y = 0.f; }  // :385-390
+          v.x = y;
+        }
+      }
+      if (!q.packed && LB != P && i < P) { v.y = -v.y; v = cmul(v, (q.m.tw + LB)[i]); }      // Bluestein: a = conj(x) w
+      A[i] = v;
+    }
+    __syncthreads();
+    float2* X = mini_fft<-1>(A, B, q.m, tid, nthr);
+    float scale = 1.0f;
+    if (!q.packed && LB != P) {
+      const float2* __restrict__ fb = q.m.tw + LB + P;
+      for (int j = tid; j < LB; j += nthr) X[j] = cmul(X[j], fb[j]);            // F(a) F(b)
+      __syncthreads();
+      X = mini_fft<+1>(X, (X == A) ? B : A, q.m, tid, nthr);                    // M (a (*) b); |.| of entry n is M |F(x)_n|
+      scale = 1.0f / (float)LB;
+    }
+    float* __restrict__ row = q.part + ((size_t)sl * q.max_avg + seg) * (size_t)q.max_bins;
+    const int bc = d.bin_count, half = bc / 2;
+    // real front end (:396-406): bins i < bc/2 read b0 + i, the others b0 + i - bc; the walk ends at the first i whose read index
+    // -- taken BEFORE the wrap at i == bc/2 -- has reached fft_n/2 + 1, and everything from there on stays zero
+    const int H = P / 2 + 1, b0 = d.shift >= 0 ? d.shift : P / 2 + d.shift;
+    const int stop = (H - b0 <= half) ? (H - b0 > 0 ? H - b0 : 0) : bc;
+    for (int i = tid; i < bc; i += nthr) {
+      int binp; bool ok;
+      if (q.complex_in) {                                                       // :477-488
+        const int off = i < half ? i : i - bc, b = d.shift + off;
+        ok = !(b < -(P / 2) || b >= (P + 1) / 2);
+        binp = b >= 0 ? b : b + P;
+      } else {
+        binp = i < half ? b0 + i : b0 + i - bc;
+        ok = i < stop && binp >= 0 && binp < H;                                 // (a negative index is outside the front end's coverage)
+      }
+      float pw = 0.f;
+      if (ok) {
+        float2 x;
+        if (q.packed) {                                                         // Hermitian split of the packed transform at bin binp (0..P/2)
+          const float2 zk = X[binp == LB ? 0 : binp], zm = X[binp == 0 ? 0 : LB - binp];
+          const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));      // (Z_k + conj Z_{H-k}) / 2
+          const float2 o = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));     // -i/2 (Z_k - conj Z_{H-k})
+          const float2 t = cmul(o, q.tw_split[binp]);
+          x = make_float2(e.x + t.x, e.y + t.y);
+        } else x = X[binp];
+        const double re = (double)(x.x * scale), im = (double)(x.y * scale);
+        const double p = re * re + im * im;                                     // cnrm() of the promoted value
+        pw = (float)p;
+        if (!(fabsf(pw) <= 3.4028234e38f)) pw = 0.f;                            // isfinite(p), :404
+      }
+      row[i] = pw;
+    }
+    __syncthreads();                                                            // the next item overwrites both buffers
+  }
+}
+
+__global__ void __launch_bounds__(256) welch_sum(WelchParams q) {
+  HIP_DYNAMIC_SHARED(double, red)                                               // [2][4]: per-wave minima, then maxima
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int sl = q.list[blockIdx.x];
+  const WelchSlot d = q.slot[sl];
+  const float* __restrict__ part = q.part + (size_t)sl * q.max_avg * (size_t)q.max_bins;
+  float* __restrict__ out = q.bins + (size_t)sl * q.max_bins;
+  double mn = (double)INFINITY, mx = 0.0;                                       // :498-499
+  for (int i = tid; i < d.bin_count; i += nthr) {
+    float bin = 0.f;
+    for (int s = 0; s < d.fft_avg; s++) {
+      const double t = (double)bin + d.gain * (double)part[(size_t)s * q.max_bins + i];
+      bin = (float)t;
+    }
+    out[i] = bin;
+    if ((double)bin < mn) mn = (double)bin;
+    if ((double)bin > mx) mx = (double)bin;
+  }
+  mn = wave_min(mn); mx = wave_max(mx);
+  if ((tid & 63) == 0) { red[tid >> 6] = mn; red[4 + (tid >> 6)] = mx; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < (nthr + 63) / 64; w++) { if (red[w] < mn) mn = red[w]; if (red[4 + w] > mx) mx = red[4 + w]; }
+    q.minmax[2 * (size_t)sl] = mn; q.minmax[2 * (size_t)sl + 1] = mx;
+  }
+}
+
 }  // namespace chz

@@ -104,6 +104,37 @@ inline int launch_chan_any(const ChanGeom& g, int nch, hipStream_t s, const Chan
   else { CHZ_LAUNCH(chan_any<false>, nch, g.any_threads, g.lds, s, e0, e1, q); }
   return 0;
 }
+// Welch power spectra (welch_seg + welch_sum): g is build_chan_geom(fft_n) -- the stage list, the Bluestein length and the LDS / global
+// scratch decision of chan_any serve the forward transform unchanged.  scratch_wgs: workgroups the caller's scratch holds (BIG only);
+// the kernel walks its work items with a grid stride, so fewer workgroups than items is fine.  With q.packed set, g and tw are those of
+// fft_n/2 points and q.tw_split the fft_n-point table.
+inline int welch_prepare() {
+#if defined(__HIPCC__) && !defined(HIPEMU)
+  static int done = -1;
+  if (done < 0) done = hipFuncSetAttribute(reinterpret_cast<const void*>(welch_seg<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess ? 1 : 0;
+  return done == 1 ? 0 : -1;
+#else
+  return 0;
+#endif
+}
+inline int launch_welch(const ChanGeom& g, WelchParams q, const float2* tw, int scratch_wgs, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
+  if (q.nslots <= 0) return 0;
+  if (q.segs > 0) {
+    q.m.N = g.lb; q.m.olen = 0; q.m.nstages = g.nstages; q.m.tw = tw;
+    for (int i = 0; i < g.nstages; i++) q.m.radix[i] = g.radix[i];
+    const long items = (long)q.nslots * q.segs;
+    if (g.big) {
+      if (!q.scratch || scratch_wgs < 1) return -1;
+      const int grid = (int)(items < scratch_wgs ? items : scratch_wgs);
+      CHZ_LAUNCH(welch_seg<true>, grid, g.any_threads, 0, s, e0, nullptr, q);
+    } else {
+      const int grid = (int)(items < 65536 ? items : 65536);
+      CHZ_LAUNCH(welch_seg<false>, grid, g.any_threads, g.lds, s, e0, nullptr, q);
+    }
+  }
+  CHZ_LAUNCH(welch_sum, q.nslots, 256, 8 * sizeof(double), s, (q.segs > 0 ? (hipEvent_t) nullptr : e0), e1, q);
+  return 0;
+}
 inline int launch_notch_fix(hipStream_t s, const NotchFixParams& p, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
   if (p.n <= 0) return 0;
   if (p.n > 1024) return -1;

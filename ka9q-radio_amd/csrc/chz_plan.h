@@ -319,39 +319,41 @@ inline void host_fft_pow2(std::vector<std::complex<double>>& x) {
       }
   }
 }
-inline bool build_chan_geom(int P, ChanGeom& g) {
-  if (!chan_menu_lookup(P, &g.r)) {
-    if (P < 8 || P > CHZ_ANY_MAX_P) return false;
-    g.P = P; g.any = true;
-    if (!mini_factor(P, g.radix, &g.nstages)) {                 // a prime factor above 13: Bluestein over M = 2^k >= 2P - 1
-      int M = 16;
-      while (M < 2 * P - 1) M <<= 1;
-      if (M > CHZ_ANY_MAX_P || !mini_factor(M, g.radix, &g.nstages)) return false;      // (chirp-z needs M >= 2P - 1 points per buffer)
-      g.blue_M = M;
-      g.tw_any.resize((size_t)M + (size_t)P + (size_t)M);
-      for (int k = 0; k < M; k++) g.tw_any[(size_t)k] = root_of_unity(k, M, -1);
-      // chirp w_n = e^{+i pi n^2 / P}, the angle reduced exactly: n^2 mod 2P over 2P
-      std::vector<std::complex<double>> b((size_t)M, std::complex<double>(0.0, 0.0));
-      for (long long n = 0; n < P; n++) {
-        const long long q = (n * n) % (2LL * P);
-        g.tw_any[(size_t)M + (size_t)n] = root_of_unity(q, 2LL * P, +1);
-        const double ang = M_PI * (double)q / (double)P;
-        const std::complex<double> cw(std::cos(ang), -std::sin(ang));       // conj(w_n)
-        b[(size_t)n] = cw;
-        if (n > 0) b[(size_t)(M - n)] = cw;
-      }
-      host_fft_pow2(b);
-      for (int k = 0; k < M; k++) g.tw_any[(size_t)M + (size_t)P + (size_t)k] = f2{(float)b[(size_t)k].real(), (float)b[(size_t)k].imag()};
-    } else {
-      g.tw_any.resize((size_t)P);
-      for (int k = 0; k < P; k++) g.tw_any[(size_t)k] = root_of_unity(k, P, -1);
+// the one-workgroup-per-transform geometry of any P from 8 to CHZ_ANY_MAX_P points (chan_any; welch_seg uses it for every fft_n)
+inline bool build_any_geom(int P, ChanGeom& g) {
+  if (P < 8 || P > CHZ_ANY_MAX_P) return false;
+  g.P = P; g.any = true;
+  if (!mini_factor(P, g.radix, &g.nstages)) {                 // a prime factor above 13: Bluestein over M = 2^k >= 2P - 1
+    int M = 16;
+    while (M < 2 * P - 1) M <<= 1;
+    if (M > CHZ_ANY_MAX_P || !mini_factor(M, g.radix, &g.nstages)) return false;      // (chirp-z needs M >= 2P - 1 points per buffer)
+    g.blue_M = M;
+    g.tw_any.resize((size_t)M + (size_t)P + (size_t)M);
+    for (int k = 0; k < M; k++) g.tw_any[(size_t)k] = root_of_unity(k, M, -1);
+    // chirp w_n = e^{+i pi n^2 / P}, the angle reduced exactly: n^2 mod 2P over 2P
+    std::vector<std::complex<double>> b((size_t)M, std::complex<double>(0.0, 0.0));
+    for (long long n = 0; n < P; n++) {
+      const long long q = (n * n) % (2LL * P);
+      g.tw_any[(size_t)M + (size_t)n] = root_of_unity(q, 2LL * P, +1);
+      const double ang = M_PI * (double)q / (double)P;
+      const std::complex<double> cw(std::cos(ang), -std::sin(ang));       // conj(w_n)
+      b[(size_t)n] = cw;
+      if (n > 0) b[(size_t)(M - n)] = cw;
     }
-    g.lb = g.blue_M ? g.blue_M : P;
-    g.any_threads = g.lb <= 1024 ? 128 : g.lb <= 2048 ? 256 : g.lb <= 4096 ? 512 : 1024;
-    g.big = g.lb > CHZ_ANY_LDS_P;
-    g.lds = g.big ? 0 : sizeof(f2) * 2 * (size_t)g.lb;
-    return true;
+    host_fft_pow2(b);
+    for (int k = 0; k < M; k++) g.tw_any[(size_t)M + (size_t)P + (size_t)k] = f2{(float)b[(size_t)k].real(), (float)b[(size_t)k].imag()};
+  } else {
+    g.tw_any.resize((size_t)P);
+    for (int k = 0; k < P; k++) g.tw_any[(size_t)k] = root_of_unity(k, P, -1);
   }
+  g.lb = g.blue_M ? g.blue_M : P;
+  g.any_threads = g.lb <= 1024 ? 128 : g.lb <= 2048 ? 256 : g.lb <= 4096 ? 512 : 1024;
+  g.big = g.lb > CHZ_ANY_LDS_P;
+  g.lds = g.big ? 0 : sizeof(f2) * 2 * (size_t)g.lb;
+  return true;
+}
+inline bool build_chan_geom(int P, ChanGeom& g) {
+  if (!chan_menu_lookup(P, &g.r)) return build_any_geom(P, g);
   g.P = P;
   g.lpc = g.r.r1 > g.r.r2 ? g.r.r1 : g.r.r2;
   g.cpw = 64 / g.lpc;

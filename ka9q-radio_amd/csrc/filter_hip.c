@@ -47,6 +47,15 @@
 #include <linux/futex.h>
 #include "../../include/ka9q_filter_abi.h"
 #include "../../include/chz_engine.h"
+/* the wideband analyser's entry points are optional: an engine library without them (a test stub) still links, and
+   ka9q_hip_spectrum() then reports -1 */
+#pragma weak chz_welch_create
+#pragma weak chz_welch_destroy
+#pragma weak chz_welch_set_window
+#pragma weak chz_welch_configure
+#pragma weak chz_welch_poll
+#pragma weak chz_welch_read_async
+#pragma weak chz_engine_info            /* used by ka9q_hip_spectrum() only */
 
 /* Environment: the shipped library reads the operator's variables only.  Tuning / A-B hooks of earlier rounds
    (KA9Q_HIP_WAKE, KA9Q_HIP_WAKE_SHARDS, KA9Q_HIP_BANK_CHANNELS, KA9Q_HIP_MINI, KA9Q_HIP_MINI_POOL) exist in -DCHZ_EXPERIMENTS builds only. */
@@ -168,6 +177,13 @@ struct mctx {
      wake_fan more (KA9Q_HIP_WAKE="first,fan"; default "0,2") */
   int wake_first, wake_fan;
   int wedged_ms;                    /* how long the producer waits for a device that completes nothing and reports nothing before it gives up (KA9Q_HIP_WEDGED_MS) */
+  /* ka9q_hip_spectrum(): welch banks of the first device's engine by fft_n (they die with that engine) */
+#define WELCH_CACHE 4
+  struct { int fft_n, id, max_bins, max_avg; bool have_window; uint64_t window_fp; } welch[WELCH_CACHE];
+  int nwelch, welch_next;
+  unsigned welch_epoch;             /* engines sh[0] has had: an analysis that spans a recovery gives up */
+  pthread_mutex_t welch_lock;       /* one analysis at a time */
+  unsigned welch_flag;              /* raised by the polls' stream behind the analysis in flight (futex word) */
   void *retired_mini;               /* an undecided small master became this engine in place: its old context (see create_input_impl) */
   int bank_cap0;                    /* channels a new bank starts with (KA9Q_HIP_BANK_CHANNELS, default 64; banks double as they fill) */
   /* KA9Q_HIP_PROFILE=1: where a block's host time goes, printed by delete_filter_input */
@@ -511,6 +527,7 @@ static void mctx_free(struct mctx *c) {          /* host side (and the communica
   }
   free(c->retired_mini);
   pthread_mutex_destroy(&c->lock);
+  pthread_mutex_destroy(&c->welch_lock);
   for (int i = 0; i < STAGE_SHARDS; i++) pthread_rwlock_destroy(&c->stage_lock[i].l);
   pthread_mutex_destroy(&c->miss_lock);
   pthread_cond_destroy(&c->miss_cv);
@@ -644,6 +661,7 @@ static int create_input_impl(struct filter_in *master, int const L, int const M,
   { const char *ws = XENV("KA9Q_HIP_WAKE_SHARDS"); if (ws) { int v = atoi(ws); if (v >= 1 && v <= WSHARDS_MAX) c->wshards = v; } }
   { const char *ns = getenv("KA9Q_HIP_NOISE_SAMPRATE"); if (ns && atof(ns) > 0) c->noise_samprate = atof(ns); }
   pthread_mutex_init(&c->lock, NULL);
+  pthread_mutex_init(&c->welch_lock, NULL);
   for (int i = 0; i < STAGE_SHARDS; i++) pthread_rwlock_init(&c->stage_lock[i].l, NULL);
   pthread_mutex_init(&c->miss_lock, NULL);
   pthread_cond_init(&c->miss_cv, NULL);
@@ -967,6 +985,7 @@ static void recover_engine(struct mctx *c, struct filter_in *f, unsigned job) {
   for (int g = 0; g < c->nsh; g++) {
     struct shard *sh = &c->sh[g];
     chz_engine_destroy(sh->eng);
+    if (g == 0) { c->nwelch = 0; c->welch_epoch++; }      /* its welch banks went with it */
     sh->eng = NULL;
     if (chz_engine_create(&sh->eng, f->ilen, f->impulse_length, f->in_type == REAL ? CHZ_REAL : CHZ_COMPLEX, sh->device, NULL, 0) != 0) {
       fprintf(stderr, "filter_hip: %s\n", chz_last_error());
@@ -1561,6 +1580,89 @@ int filter_hip_enable_noise(struct filter_in *master, double samprate) {
 double filter_hip_noise(struct filter_out const *slave) {
   if (slave == NULL || slave->rev_plan == NULL || slave->master == NULL || is_mini_master(slave->master)) return NAN;
   return ((struct sctx const *)(void const *)slave->rev_plan)->n0;
+}
+/* wideband_poll() (src/spectrum.c:308-522) on the device: fft_avg overlapping windowed segments of fft_n samples ending at the newest
+   sample the master's device ring holds (with shards: the first one's), transformed, |X|^2 of bin_count bins around `shift` summed as the
+   reference sums them into bin_data[]; minmax (may be NULL) receives min_power / max_power (:498-507).  Synchronous.  Returns the
+   effective fft_avg (limited to the data on hand, :359-361), -1 for a master without a device ring (inline / mini) or an engine
+   library without the analyser. */
+static void welch_note(void *arg) { __atomic_store_n((unsigned *)arg, 1u, __ATOMIC_RELEASE); futex_wake_all((unsigned *)arg); }
+int ka9q_hip_spectrum(struct filter_in *master, int fft_n, const float *window, int shift, int bin_count, int fft_avg, double overlap,
+                      float *bin_data, double minmax[2]) {
+  if (!chz_engine_info || !chz_welch_create || !chz_welch_destroy || !chz_welch_set_window || !chz_welch_configure || !chz_welch_poll || !chz_welch_read_async) return -1;
+  if (master == NULL || master->fwd_plan == NULL || is_mini_master(master)) return -1;
+  if (window == NULL || bin_data == NULL || fft_n < 1 || bin_count < 1 || fft_avg < 1 || !(overlap >= 0 && overlap < 1)) return -1;
+  struct mctx *c = MCTX(master);
+  int rc = -1;
+  /* the window's fingerprint, taken before any lock: the upload (up to 4 MB) is skipped while the caller's window stays what the bank holds */
+  uint64_t fp = 1469598103934665603ull;
+  for (int i = 0; i < fft_n; i++) { uint32_t u; memcpy(&u, &window[i], sizeof u); fp = (fp ^ u) * 1099511628211ull; }
+  /* one analysis at a time (the banks hold one analyser each); c->lock -- the lock every block is enqueued under -- is held only to find
+     or make the bank and to ISSUE the work, never across a wait for the device */
+  pthread_mutex_lock(&c->welch_lock);
+  pthread_mutex_lock(&c->lock);
+  chz_engine *const eng = c->sh[0].eng;
+  unsigned const epoch = c->welch_epoch;                  /* a recovery that replaces the engine moves it on */
+  chz_info info;
+  int k = -1, id = -1, mb = 0, eff = -1;
+  if (chz_engine_info(eng, &info) != 0) goto unlock;
+  long long const ring = (long long)info.ring_blocks * info.L;
+  if (fft_n > ring) goto unlock;
+  double const lim = floor(1 + (double)(ring / fft_n - 1) / (1 - overlap));
+  int const need = (double)fft_avg > lim ? (int)lim : fft_avg;
+  for (int i = 0; i < c->nwelch; i++) if (c->welch[i].fft_n == fft_n) k = i;
+  int want_bins = bin_count, want_avg = need;
+  if (k >= 0 && (c->welch[k].max_bins < bin_count || c->welch[k].max_avg < need)) {      /* outgrown: replaced by one that holds the old AND the new request */
+    if (c->welch[k].max_bins > want_bins) want_bins = c->welch[k].max_bins;
+    if (c->welch[k].max_avg > want_avg) want_avg = c->welch[k].max_avg;
+    chz_welch_destroy(eng, c->welch[k].id);
+    c->welch[k].fft_n = 0;
+  } else if (k < 0) {
+    if (c->nwelch < WELCH_CACHE) k = c->nwelch++;
+    else { k = c->welch_next; c->welch_next = (c->welch_next + 1) % WELCH_CACHE; chz_welch_destroy(eng, c->welch[k].id); }
+    c->welch[k].fft_n = 0;
+  }
+  if (c->welch[k].fft_n == 0) {
+    int const nid = chz_welch_create(eng, fft_n, 1, want_bins, want_avg);
+    if (nid < 0) { c->welch[k] = c->welch[--c->nwelch]; goto unlock; }
+    c->welch[k].fft_n = fft_n; c->welch[k].id = nid; c->welch[k].max_bins = want_bins; c->welch[k].max_avg = want_avg; c->welch[k].have_window = false;
+  }
+  id = c->welch[k].id; mb = c->welch[k].max_bins;
+  bool const upload = !c->welch[k].have_window || c->welch[k].window_fp != fp;
+  pthread_mutex_unlock(&c->lock);
+  /* window and parameters travel in the polls' own stream (the calls wait for that stream only); the engine cannot go away meanwhile
+     without welch_epoch moving: a recovery takes c->lock, and every engine call below is made under it */
+  float *rows = malloc(sizeof(float) * (size_t)mb);
+  double mm[2] = {0, 0};
+  if (rows == NULL) { pthread_mutex_unlock(&c->welch_lock); return -1; }
+  pthread_mutex_lock(&c->lock);
+  if (epoch == c->welch_epoch) {
+    if (upload && chz_welch_set_window(eng, id, 0, window) == 0) { c->welch[k].have_window = true; c->welch[k].window_fp = fp; }
+    if (c->welch[k].have_window) eff = chz_welch_configure(eng, id, 0, shift, bin_count, fft_avg, overlap);
+    __atomic_store_n(&c->welch_flag, 0u, __ATOMIC_RELEASE);
+    if (eff >= 1 && (chz_welch_poll(eng, id, 1, NULL, -1) != 0 || chz_welch_read_async(eng, id, 0, 1, rows, mm) != 0 ||
+                     chz_host_callback(eng, CHZ_SLOT_WELCH, welch_note, &c->welch_flag) != 0)) {
+      if (eff >= 1) chz_sync(eng);                      /* something may be in flight towards rows / mm: drain before they go away */
+      eff = -1;
+    }
+  }
+  pthread_mutex_unlock(&c->lock);
+  if (eff >= 1) {
+    /* the wait for the poll: outside c->lock, on a word the polls' stream raises -- no engine call, so a recovery may replace the
+       engine meanwhile (destroying an engine drains its streams, the word is raised either way); the epoch tells */
+    while (__atomic_load_n(&c->welch_flag, __ATOMIC_ACQUIRE) == 0) futex_wait_u32(&c->welch_flag, 0);
+    pthread_mutex_lock(&c->lock);
+    bool const same = epoch == c->welch_epoch;
+    pthread_mutex_unlock(&c->lock);
+    if (same) { memcpy(bin_data, rows, sizeof(float) * (size_t)bin_count); if (minmax) { minmax[0] = mm[0]; minmax[1] = mm[1]; } rc = eff; }
+  }
+  free(rows);
+  pthread_mutex_unlock(&c->welch_lock);
+  return rc;
+unlock:
+  pthread_mutex_unlock(&c->lock);
+  pthread_mutex_unlock(&c->welch_lock);
+  return -1;
 }
 /* returns once the device has finished every block handed to it so far (an orderly shutdown reads its last results after this) */
 int filter_hip_drain(struct filter_in *master) {

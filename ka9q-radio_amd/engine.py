@@ -67,6 +67,7 @@ SYMBOLS = [
     "chz_mini_create", "chz_mini_destroy", "chz_mini_capacity", "chz_mini_add", "chz_mini_release", "chz_mini_set_response", "chz_mini_execute",
     "chz_comm_barrier", "chz_comm_allreduce_max", "chz_spectrum_broadcast", "chz_spectrum_exchange_rows", "chz_run_blocks_sharded",
     "chz_comm_create_local", "chz_spectrum_broadcast_local", "chz_set_option",
+    "chz_welch_create", "chz_welch_destroy", "chz_welch_set_window", "chz_welch_configure", "chz_welch_poll", "chz_welch_read", "chz_welch_read_async",
 ]
 
 # the CHZ_* variables tests and scripts have always used to force a code path or arm a test hook: the shipped library does not read
@@ -168,6 +169,13 @@ def lib():
         L.chz_step.argtypes = [_vp, _u]
         L.chz_run_blocks.argtypes = [_vp, _u, _i, _i, _i, C.POINTER(ChzTiming)]
         L.chz_gather_descriptor.argtypes = [_i, _i, _i, _i, C.POINTER(_i * 6)]
+        L.chz_welch_create.argtypes = [_vp, _i, _i, _i, _i]
+        L.chz_welch_destroy.argtypes = [_vp, _i]
+        L.chz_welch_set_window.argtypes = [_vp, _i, _i, _vp]
+        L.chz_welch_configure.argtypes = [_vp, _i, _i, _i, _i, _i, _d]
+        L.chz_welch_poll.argtypes = [_vp, _i, _i, _vp, C.c_longlong]
+        L.chz_welch_read.argtypes = [_vp, _i, _i, _i, _vp, _vp]
+        L.chz_welch_read_async.argtypes = [_vp, _i, _i, _i, _vp, _vp]
         _lib = L
     return _lib
 
@@ -311,6 +319,18 @@ class Engine:
         b = Bank(self, P, olen, capacity, real, shared_rows)
         self.banks.append(b)
         return b
+
+    def welch(self, fft_n, capacity, max_bins, max_avg, packed=None):
+        """A bank of wideband spectrum analysers (wideband_poll(), src/spectrum.c:308-522) on the samples of the input ring.
+        packed: None = the library's default; True / False = option welch_packed for this bank (real front end, even fft_n:
+        half-length packed transform with a Hermitian split instead of the full-length complex transform)."""
+        if packed is not None:
+            _check(lib().chz_set_option(b"welch_packed", b"1" if packed else b"0"))
+        try:
+            return Welch(self, fft_n, capacity, max_bins, max_avg)
+        finally:
+            if packed is not None:
+                _check(lib().chz_set_option(b"welch_packed", None))
 
     def step(self, job):
         _check(lib().chz_step(self._h, job & 0xFFFFFFFF))
@@ -492,6 +512,52 @@ class Bank:
         p = _vp()
         _check(lib().chz_bank_output_device(self.eng._h, self.id, slot, C.byref(p)))
         return p.value
+
+
+class Welch:
+    """chz_welch_*: `capacity` analysers sharing one fft_n; one poll serves any number of them."""
+
+    def __init__(self, eng, fft_n, capacity, max_bins, max_avg):
+        self.eng, self.fft_n, self.capacity, self.max_bins, self.max_avg = eng, fft_n, capacity, max_bins, max_avg
+        self.id = _check(lib().chz_welch_create(eng._h, fft_n, capacity, max_bins, max_avg))
+        self.bin_count = [0] * capacity
+        self.fft_avg = [0] * capacity
+
+    def set_window(self, slot, window):
+        w = np.ascontiguousarray(window, np.float32).reshape(-1)
+        assert w.shape[0] == self.fft_n
+        _check(lib().chz_welch_set_window(self.eng._h, self.id, slot, w.ctypes.data))
+
+    def configure(self, slot, shift, bin_count, fft_avg, overlap):
+        """Returns the effective fft_avg (limited to the data the device ring holds, src/spectrum.c:359-361)."""
+        eff = _check(lib().chz_welch_configure(self.eng._h, self.id, slot, int(shift), int(bin_count), int(fft_avg), float(overlap)))
+        self.bin_count[slot], self.fft_avg[slot] = int(bin_count), eff
+        return eff
+
+    def poll(self, slots=None, end=None):
+        """slots: analysers to serve (default: every configured one); end: ring position just past the newest sample of the
+        window (default: everything written so far).  Asynchronous; read() waits."""
+        if slots is None:
+            slots = [s for s in range(self.capacity) if self.fft_avg[s] > 0]
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        self._polled = [int(s) for s in sl]
+        if sl.shape[0]:
+            _check(lib().chz_welch_poll(self.eng._h, self.id, sl.shape[0], sl.ctypes.data, -1 if end is None else int(end)))
+
+    def read(self, slots=None):
+        """(bins, minmax): per analyser of the latest poll (or of `slots`) its bin_count float32 bins in the reference's FFT order
+        and float64 (min_power, max_power)."""
+        if slots is None:
+            slots = getattr(self, "_polled", [])
+        rows = np.zeros((self.capacity, self.max_bins), np.float32)
+        mm = np.zeros((self.capacity, 2), np.float64)
+        _check(lib().chz_welch_read(self.eng._h, self.id, 0, self.capacity, rows.ctypes.data, mm.ctypes.data))
+        return [rows[s, :self.bin_count[s]].copy() for s in slots], [mm[s].copy() for s in slots]
+
+    def close(self):
+        if self.id is not None and self.eng._h:
+            _check(lib().chz_welch_destroy(self.eng._h, self.id))
+        self.id = None
 
 
 COMM_ID_BYTES = 128
