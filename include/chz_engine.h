@@ -427,6 +427,46 @@ int chz_welch_poll(chz_engine *e, int bank, int nslots, const int *slots, long l
 int chz_welch_read(chz_engine *e, int bank, int slot0, int n, float *bins, double *minmax);
 int chz_welch_read_async(chz_engine *e, int bank, int slot0, int n, float *bins, double *minmax);
 
+/* ---- Welch power spectra of a channel's baseband: radiod's narrowband spectrum analyser (narrowband_poll(), src/spectrum.c:206-306, fed by
+ * demod_spectrum(), :123-155) on the output rows a COMPLEX-output channel bank leaves in HBM.  chz_bank_welch_create makes a bank of
+ * `capacity` analysers sharing one fft_n (any length chz_welch_create takes), in the id space of chz_welch_create: chz_welch_set_window,
+ * chz_welch_read, chz_welch_read_async (CHZ_SLOT_WELCH) and chz_welch_destroy serve both kinds; chz_welch_configure / _poll refuse a bank
+ * of this kind with a message, and the calls below refuse a bank of chz_welch_create.  REAL-output banks are refused.
+ * Each attached analyser owns a device ring of max_avg * fft_n + (CHZ_ND + 1) * olen complex samples, zeros at attach like the
+ * reference's fresh ring (:142-144).  From then on every execution of the bank (chz_step, chz_run_blocks, chz_bank_execute[_range]) copies
+ * the analyser's channel row of block `job` to ring position ((job - job0) * olen) mod ring length, right behind the channel kernel on
+ * the block's own stream (kernel bb_ring_append): a closed form in the block number, so a re-run of a block (chz_bank_execute_range)
+ * rewrites the samples it wrote before, and blocks before job0 write nothing.  A bank without attached analysers pays nothing.  With
+ * chz_bank_set_tuning the rows carry downconvert()'s fine rotation, as chan->baseband does.
+ * Per analyser and poll, narrowband_poll()'s arithmetic: fft_avg segments walking FORWARDS from end - lrint(fft_n (1 + (fft_avg - 1)
+ * (1 - overlap))) (:247) with hop = fft_n - lrint(fft_n overlap) (:278), each times the window, transformed, and gain |X[fr]|^2 added
+ * bin by bin in iteration order in the reference's types, gain = 1 / (fft_n^2 fft_avg) (:255, no factor 2), fr = i for
+ * i < bin_count / 2, then fft_n - bin_count / 2 + (i - bin_count / 2) (:267-276, no shift); min and max as :284-293.  Where the two
+ * roundings carry the last segment past the end of the window, the reference's ring of fft_avg * fft_n samples wraps onto its oldest
+ * samples; the device reads those same samples (fft_avg * fft_n further back).  For an ODD bin_count the reference's last bin would
+ * read X[fft_n], which its own assert (:271) forbids: the device leaves that bin zero.  bin_count > fft_n and fft_avg > max_avg are
+ * refused; fft_avg is not clamped (the reference's limit never binds, :242-246).  A configuration that needs a longer ring
+ * (max_avg, fft_n) takes a new bank: rings start as zeros.
+ * Graph replay: chz_run_blocks(mode 1) is REFUSED with a message while any bank has attached analysers (the block number is baked into
+ * captured launches); attach, detach, configure and destroy drop a captured graph like every configuration change. */
+int chz_bank_welch_create(chz_engine *e, int bank, int fft_n, int capacity, int max_bins, int max_avg);
+/* analyser `slot` follows channel `channel` of the bank from block job0 on (the next block to be executed, or -- with a
+ * chz_bank_execute_range of it afterwards -- the one just executed).  Drains the engine.  Detach stops the copies. */
+int chz_bank_welch_attach(chz_engine *e, int welch, int slot, int channel, unsigned job0);
+int chz_bank_welch_detach(chz_engine *e, int welch, int slot);
+/* returns the effective fft_avg (= fft_avg), < 0: error */
+int chz_bank_welch_configure(chz_engine *e, int welch, int slot, int bin_count, int fft_avg, double overlap);
+/* one launch pair for analysers slots[0..nslots) (NULL: 0..nslots-1) on the polls' stream; the window ends just past block `job`'s
+ * samples.  Ordered behind the ring appends of every block issued so far (one event per slot); blocks job+1 .. job+CHZ_ND may be in
+ * flight or issued meanwhile -- the ring's slack keeps them out of the window -- and the append of a later block that would overwrite
+ * samples an unfinished poll still reads waits for that poll (one event; the whole ring is taken as one); other appends do not wait.
+ * Refused: a job not issued yet, one from before an analyser's attach, and one more than CHZ_ND blocks behind the newest issued. */
+int chz_bank_welch_poll(chz_engine *e, int welch, int nslots, const int *slots, unsigned job);
+
+/* host-side helper exposed for tests: out3 = {hop, adjust} of chz_bank_welch_configure(fft_n, fft_avg, overlap) and the ring position of
+ * block job's first sample for an analyser attached at job0 (-1: the block lies before the attach) */
+int chz_bank_welch_steps(int fft_n, int fft_avg, double overlap, unsigned job, unsigned job0, int olen, long long ring_len, long long out3[3]);
+
 /* host-side helper exposed for tests: the closed-form gather descriptor
  * {t0,cnt,src0,dir,conj,wrap} that restates src/filter.c:728-911 */
 int chz_gather_descriptor(int in_type, int master_bins, int P, int shift, int out6[6]);

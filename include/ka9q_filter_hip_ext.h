@@ -52,6 +52,19 @@ void filter_hip_set_exit_hook(void (*hook)(void));
  * prefix is pinned by the exported-symbol test.) */
 int ka9q_hip_spectrum(struct filter_in *master, int fft_n, const float *window, int shift, int bin_count, int fft_avg, double overlap,
                       float *bin_data, double minmax[2]);
+/* The narrowband spectrum analyser on the device: what narrowband_poll() (src/spectrum.c:206-306, fed by demod_spectrum(), :123-155)
+ * computes on the host from a ring of the channel's baseband -- fft_avg windowed segments of fft_n samples walking forwards, transformed,
+ * 1 / (fft_n^2 fft_avg) |X|^2 summed into bin_data[] in its bin order (no shift; an odd bin_count leaves the last bin zero, where the
+ * reference's own assert :271 would fail) -- computed from the rows a COMPLEX slave's channel leaves on the device, ending with the block
+ * the slave's last execute_filter_output() delivered.  The first call for a (slave, fft_n) attaches the analyser: it follows the channel
+ * from the NEXT block the master issues, history before that is zeros like the reference's fresh ring (:142-144), and that first call
+ * therefore reports zeros.  A larger fft_avg, a moved or re-created bank start a fresh ring of zeros too.  window = fft_n floats, cached
+ * by content.  LIMIT: the drop-in's banks are untuned, so this is the spectrum BEFORE downconvert()'s fine rotation; it is
+ * narrowband_poll()'s only where chan->filter.remainder is zero.  Synchronous.  Returns fft_avg; -1 for a slave of an inline (small)
+ * master, a REAL slave, a slave more than four blocks behind its master, bin_count > fft_n or other bad arguments, or an engine
+ * library without the analyser. */
+int ka9q_hip_spectrum_narrow(struct filter_out *slave, int fft_n, const float *window, int bin_count, int fft_avg, double overlap,
+                             float *bin_data, double minmax[2]);
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@
 #include <functional>
 #include <mutex>
 #include <string>
+#include <algorithm>
 #include <vector>
 #include <thread>
 #include <cmath>
@@ -136,6 +137,17 @@ struct Bank {
   double* n0 = nullptr;         // [ND][cap] estimate_noise() (src/radio.c:1783-1866)
   unsigned* noise_hint = nullptr;   // [cap] the binade the channel's quantile fell into last time (noise_est: a guess it verifies, never a result)
   double noise_samprate = 0.0;  // front-end sample rate; 0 = off
+  // narrowband analysers attached to this bank's channels (chz_bank_welch_*, chz_welch.inc).  bb_n == 0 -- the usual case -- costs a block
+  // nothing: no launch, no event.  The list is rewritten by attach / detach on a drained engine only; what the two issuing threads of
+  // chz_run_blocks touch is per slot (ev_bb, bb_rec) or atomic (bb_newest, bb_busy).
+  BbRing* bb = nullptr;         // device [bb_n], sorted by channel
+  std::vector<BbRing> bb_h;     // what `bb` holds
+  int bb_n = 0;
+  hipEvent_t ev_bb[CHZ_ND] = {nullptr, nullptr, nullptr, nullptr};     // behind the slot's latest ring append
+  bool bb_rec[CHZ_ND] = {false, false, false, false};
+  unsigned bb_newest = 0;                         // the newest block whose append has been issued (job0 - 1 of the first attach: none yet)
+  hipEvent_t bb_done = nullptr;                   // on the polls' stream behind the latest poll of this bank's analysers
+  int bb_busy = 0; unsigned bb_guard = 0;         // an unfinished poll may still read ring samples that the append of a block after bb_guard overwrites
 };
 
 // A lane = one HIP stream + its own intermediate buffer.  Consecutive blocks go to
@@ -294,6 +306,7 @@ template <class T> static int upload(T** dst, const std::vector<f2>& v) {
 }
 
 static void welch_free_all(chz_engine* e);      // chz_welch.inc
+static void welch_bank_gone(chz_engine* e, int bank);      // chz_welch.inc: a channel bank is destroyed, its analysers are detached
 // in front of an input write of n samples at ring position pos: the write waits for an unfinished poll that reads any of them
 static int welch_guard(chz_engine* e, long long pos, long long n) {
   if (!e->welch_busy || n <= 0) return 0;
@@ -321,6 +334,10 @@ static void free_bank(Bank& b) {
     if (b.ev_pcmgo[s]) (void)hipEventDestroy(b.ev_pcmgo[s]);
     b.ev_bank[s] = b.ev_tail[s] = b.ev_pcm[s] = b.ev_pcmgo[s] = nullptr; b.tail_used[s] = false; b.pcm_copying[s] = false;
   }
+  hipFree(b.bb); b.bb = nullptr; b.bb_h.clear(); b.bb_n = 0; b.bb_busy = 0;
+  if (b.bb_done) (void)hipEventDestroy(b.bb_done);
+  b.bb_done = nullptr;
+  for (int s = 0; s < CHZ_ND; s++) { if (b.ev_bb[s]) (void)hipEventDestroy(b.ev_bb[s]); b.ev_bb[s] = nullptr; b.bb_rec[s] = false; }
   for (int s = 0; s < CHZ_ND; s++) {
     if (b.stage[s]) (void)hipHostFree(b.stage[s]);
     for (int h = 0; h < 2; h++) { if (b.stage_ev[s][h]) (void)hipEventDestroy(b.stage_ev[s][h]); b.stage_ev[s][h] = nullptr; b.stage_busy[s][h] = false; }
@@ -655,7 +672,7 @@ static int sync_all(chz_engine* e) {
   for (int i = 0; i < e->nlanes; i++) HIPOK(hipStreamSynchronize(e->lanes[i].s));
   if (e->tail) HIPOK(hipStreamSynchronize(e->tail));
   if (e->pcmcopy) HIPOK(hipStreamSynchronize(e->pcmcopy));
-  if (e->welch_s) { HIPOK(hipStreamSynchronize(e->welch_s)); e->welch_busy = false; }
+  if (e->welch_s) { HIPOK(hipStreamSynchronize(e->welch_s)); e->welch_busy = false; for (auto& b : e->banks) b.bb_busy = 0; }
   // nothing is travelling any more: the demodulator launches that follow (a graph capture among them: an eagerly recorded event is no
   // business of a capture) need not wait for the copy stream's last read of their slot
   for (auto& b : e->banks) for (int s = 0; s < CHZ_ND; s++) b.pcm_copying[s] = false;
@@ -1141,6 +1158,32 @@ static void demod_paths(const chz_engine* e, const Bank& b, DemodParams& d) {
   const bool lin_wave = b.dm_lin > 0 && (!d.lin_lanes || (b.dm_pll_lin > 0 && d.mix == nullptr));
   d.wave_any = (fm_wave || lin_wave) ? 1 : 0;
 }
+// The baseband rings of the bank's attached narrowband analysers, behind the channel kernel of block `job` on its own lane stream
+// (only called for a bank that has any).  A partial re-run covers the analysers of its channel range and rewrites the same ring
+// samples: the position is a closed form in the block number (bb_ring_append).
+// Appends run on the device in BLOCK ORDER: the lanes are independent streams, and a lane that fell a whole ring behind (an issuing
+// thread that was descheduled, say) would otherwise put its old block over the newer one that shares its ring positions.  So a
+// whole-bank append waits for its predecessor's -- whose event exists by then: chz_run_blocks hands the banks' launches from block to
+// block across its issuing threads while any analyser is attached (enqueue_step), every other caller issues from one thread.
+static int enqueue_bb_append(chz_engine* e, Bank& b, unsigned job, int slot, hipStream_t st, int ch0, int n, bool whole) {
+  const auto by_ch = [](const BbRing& a, int ch) { return a.ch < ch; };
+  const int lo = (int)(std::lower_bound(b.bb_h.begin(), b.bb_h.end(), ch0, by_ch) - b.bb_h.begin());
+  const int hi = (int)(std::lower_bound(b.bb_h.begin(), b.bb_h.end(), ch0 + n, by_ch) - b.bb_h.begin());
+  if (hi <= lo) return 0;
+  // an unfinished poll still reads samples that this block overwrites: the block waits for it (the whole ring taken as one, like welch_guard)
+  if (__atomic_load_n(&b.bb_busy, __ATOMIC_ACQUIRE) && (int)(job - b.bb_guard) > 0) HIPOK(hipStreamWaitEvent(st, b.bb_done, 0));
+  const int prev = (slot + CHZ_ND - 1) % CHZ_ND;
+  if (whole && b.bb_rec[prev]) HIPOK(hipStreamWaitEvent(st, b.ev_bb[prev], 0));
+  BbAppendParams q{};
+  q.out = bank_out(b, slot); q.list = b.bb; q.first = lo; q.olen = b.olen; q.job = job;
+  launch_bb_append(q, hi - lo, st);
+  HIPOK(hipEventRecord(b.ev_bb[slot], st));           // what a poll waits for
+  b.bb_rec[slot] = true;
+  // the newest block issued (the first attach set it to job0 - 1); a partial run fills some analysers' rings only and does not count
+  unsigned cur = __atomic_load_n(&b.bb_newest, __ATOMIC_RELAXED);
+  while (whole && (int)(job - cur) > 0 && !__atomic_compare_exchange_n(&b.bb_newest, &cur, job, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+  return 0;
+}
 static int enqueue_bank(chz_engine* e, int bank, unsigned job, Instr* in, int ch0 = 0, int n = -1, bool partial = false) {
   Bank& b = e->banks[(size_t)bank];
   if (n < 0) n = b.active;
@@ -1183,6 +1226,7 @@ static int enqueue_bank(chz_engine* e, int bank, unsigned job, Instr* in, int ch
     if (launch_chan_real(b.g.r, grid, b.g.wpb * 64, b.g.lds, st, c, IN_E0(in), IN_E1(in))) return fail(-4, "no real-output kernel for P=%d", b.P);
   } else if (launch_chan(b.g.r, grid, b.g.wpb * 64, b.g.lds, st, c, IN_E0(in), IN_E1(in))) return fail(-4, "no kernel for P=%d", b.P);
   mark(in, st, 4, false);
+  if (b.bb_n > 0) { int r = enqueue_bb_append(e, b, job, slot, st, ch0, n, whole_bank); if (r) return r; }
   if (b.n0 && b.noise_samprate > 0.0) {
     NoiseParams q = noise_params(e->bins, e->in_type == CHZ_REAL, b.out_real ? b.P / 2 + 1 : b.P, b.noise_samprate);   // slave->bins
     q.spec = e->spec[slot]; q.lay = c.lay; q.desc = b.desc + so; q.n0 = b.n0 + so; q.ch0 = ch0; q.nch = n; q.magic = c.magic; q.dpitch = c.dpitch; q.hint = b.noise_hint;
@@ -1897,6 +1941,7 @@ int chz_bank_destroy(chz_engine* e, int bank) {
   Bank& b = e->banks[(size_t)bank];
   { int r = sync_all(e); if (r) return r; }
   drop_graph(e);
+  welch_bank_gone(e, bank);
   free_bank(b);
   return 0;
 }
@@ -1962,7 +2007,7 @@ static int enqueue_step(chz_engine* e, unsigned job, Instr* in, NotchTurn* turn 
   int r = enqueue_forward(e, job, in, turn, seq, capture_first, capturing);
   if (r) return r;
   bool demod = false;
-  for (const Bank& b : e->banks) demod = demod || b.dm_on > 0;
+  for (const Bank& b : e->banks) demod = demod || b.dm_on > 0 || b.bb_n > 0;      // (or feeds baseband rings: enqueue_bb_append)
   if (demod && turn) {                // what goes to the demodulator stream is issued in block order
     while (turn->next_tail.load(std::memory_order_acquire) != seq) {
       if (turn->abort.load(std::memory_order_relaxed)) return fail(-6, "another issuing thread failed");
@@ -2010,7 +2055,7 @@ int chz_run_blocks(chz_engine* e, unsigned job0, int nblocks, int mode, int inst
   if (!e || nblocks < 0) return fail(-1, "bad argument");
   if (mode == 1)
     for (const Bank& b : e->banks)
-      if (b.fine || b.dm_on) return fail(-5, "graph replay bakes the block number into the captured launches; fine-tuned and demodulated banks need eager mode");
+      if (b.fine || b.dm_on || b.bb_n) return fail(-5, "graph replay bakes the block number into the captured launches; fine-tuned and demodulated banks and banks with attached spectrum analysers need eager mode");
   HIPOK(hipSetDevice(e->device));
   { int r = sync_all(e); if (r) return r; }
   e->input_pending = false;                       // everything written so far is visible to every lane now

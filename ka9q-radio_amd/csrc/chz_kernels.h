@@ -3577,6 +3577,20 @@ struct WelchSlot {
   long long adjust;                     // samples between the first segment's start and the end of the window
   double gain;                          // 2 or 1 / (fft_avg * fft_n^2)  (:373,:431)
 };
+// One narrowband analyser's baseband history: the olen complex samples channel `ch` of its bank produces per block, block job0's at
+// ring position 0, block job's at ((job - job0) * olen) mod ring_len -- a closed form in the block number, so blocks in flight on
+// several lanes never share a write index and a re-run of a block rewrites the samples it wrote before.
+struct BbRing {
+  float2* ring; long long ring_len;     // ring_len >= max_avg * fft_n + (CHZ_ND + 1) * olen
+  unsigned job0; int ch;                // ch < 0: not attached
+};
+// where block `job`'s first sample lies in the ring of an analyser attached at block job0: the UNSIGNED difference of the block numbers
+// (which wrap at 2^32), widened before the multiplication.  *before: the block lies in front of the attach.
+__host__ __device__ inline long long bb_ring_pos(unsigned job, unsigned job0, int olen, long long ring_len, bool* before) {
+  const unsigned d = job - job0;
+  *before = d >= 0x80000000u;
+  return (long long)((unsigned long long)d * (unsigned long long)olen % (unsigned long long)ring_len);
+}
 struct WelchParams {
   const float* ring; const short* ring16; float scale16; int derand;
   long long ring_samples, end;          // ring length and (end of the window) mod ring length, in samples
@@ -3595,6 +3609,10 @@ struct WelchParams {
   // fft_n/2-point transform (m.N = fft_n/2) and bin k is recovered where it is read, X_k = (Z_k + conj Z_{H-k})/2 - i/2 W^k (Z_k - conj Z_{H-k})
   int packed;
   const float2* tw_split;               // [fft_n] e^{-2 pi i k / fft_n}
+  // baseband source (the narrowband analyser, see bb_ring_append below): bb != nullptr replaces the input ring by analyser sl's own
+  // complex ring bb[sl], and the window ends just past block bb_job's samples
+  const BbRing* bb;                     // [cap]
+  unsigned bb_job; int bb_olen;
 };
 
 template <bool BIG>
@@ -3614,7 +3632,22 @@ __global__ void __launch_bounds__(1024) welch_seg(WelchParams q) {
     long long s0 = q.end - d.adjust + (q.complex_in ? -(long long)seg : (long long)seg) * (long long)d.hop;
     s0 %= R; if (s0 < 0) s0 += R;
     const float* __restrict__ win = q.window + (size_t)sl * P;
-    const bool flip = !q.complex_in && d.shift < 0;
+    const bool flip = !q.complex_in && d.shift < 0 && !q.bb;
+    // narrowband_poll() (src/spectrum.c:247-281): segments walk FORWARDS from end - adjust with hop = fft_n - lrint(fft_n overlap).  The
+    // roundings of adjust and hop can carry the last segments a few samples past the end of the window; the reference's ring of
+    // fft_avg * fft_n samples wraps there onto its oldest ones, so those reads lie fft_avg * fft_n samples further back (bb_m1).
+    // Positions in front of the attach (negative) read the zeros the ring was created with, as the reference's fresh ring gives them.
+    const float2* bb_ring = nullptr; long long bb_RL = 1, bb_m0 = 0, bb_m1 = 0; int bb_past = 0;
+    if (q.bb) {
+      const BbRing a = q.bb[sl];
+      bb_ring = a.ring; bb_RL = a.ring_len;
+      const long long end = ((long long)(unsigned)(q.bb_job - a.job0) + 1) * (long long)q.bb_olen;
+      const long long p0 = end - d.adjust + (long long)seg * (long long)d.hop;
+      bb_m0 = p0 % bb_RL; if (bb_m0 < 0) bb_m0 += bb_RL;
+      bb_m1 = (p0 - (long long)d.fft_avg * P) % bb_RL; if (bb_m1 < 0) bb_m1 += bb_RL;
+      const long long room = end - p0;                                         // samples of this segment in front of the end; <= 0 (many short segments, e.g. fft_n 8, fft_avg 50, overlap 0.9) when it starts past it: then every sample is a wrapped one
+      bb_past = room < (long long)P ? (int)room : P;
+    }
     if (q.packed) {
       for (int i = tid; i < LB; i += nthr) {                                   // LB = P/2; the pair (2i, 2i+1)
         float x[2];
@@ -3639,7 +3672,10 @@ __global__ void __launch_bounds__(1024) welch_seg(WelchParams q) {
       if (i < P) {
         long long idx = s0 + i; if (idx >= R) idx -= R;                        // fft_n <= R
         const float w = win[i];
-        if (q.complex_in) { const float2 x = reinterpret_cast<const float2*>(q.ring)[idx]; v = make_float2(w * x.x, w * x.y); }
+        if (bb_ring) {
+          long long bi = (i < bb_past ? bb_m0 : bb_m1) + i; if (bi >= bb_RL) bi -= bb_RL;      // fft_n <= ring_len
+          const float2 x = bb_ring[bi]; v = make_float2(w * x.x, w * x.y);                        // :261
+        } else if (q.complex_in) { const float2 x = reinterpret_cast<const float2*>(q.ring)[idx]; v = make_float2(w * x.x, w * x.y); }
         else {
           float x;
           if (q.ring16 != nullptr) {
@@ -3674,7 +3710,10 @@ __global__ void __launch_bounds__(1024) welch_seg(WelchParams q) {
     const int stop = (H - b0 <= half) ? (H - b0 > 0 ? H - b0 : 0) : bc;
     for (int i = tid; i < bc; i += nthr) {
       int binp; bool ok;
-      if (q.complex_in) {                                                       // :477-488
+      if (q.bb) {                                                               // :267-276: DC upwards, then the top of the transform; no shift
+        binp = i < half ? i : P - half + (i - half);
+        ok = binp < P;                                                          // an odd bin_count's last bin would read X[fft_n] (the reference's own assert, :271): left zero
+      } else if (q.complex_in) {                                                // :477-488
         const int off = i < half ? i : i - bc, b = d.shift + off;
         ok = !(b < -(P / 2) || b >= (P + 1) / 2);
         binp = b >= 0 ? b : b + P;
@@ -3727,6 +3766,29 @@ __global__ void __launch_bounds__(256) welch_sum(WelchParams q) {
   if (tid == 0) {
     for (int w = 1; w < (nthr + 63) / 64; w++) { if (red[w] < mn) mn = red[w]; if (red[4 + w] > mx) mx = red[4 + w]; }
     q.minmax[2 * (size_t)sl] = mn; q.minmax[2 * (size_t)sl + 1] = mx;
+  }
+}
+
+// ------------------------------------------------------------------------------
+// bb_ring_append: behind a block's channel kernel, on the block's own lane stream -- one workgroup per attached narrowband
+// analyser copies its channel's olen samples of the slot's output image into the analyser's baseband ring (BbRing).  Launched
+// only for banks with attached analysers, over the analysers of the channel range the launch covered.
+// ------------------------------------------------------------------------------
+struct BbAppendParams {
+  const float2* out;                    // the slot's output image [cap][olen]
+  const BbRing* list;                   // the bank's attached analysers, sorted by channel
+  int first, olen;                      // workgroup w serves list[first + w]
+  unsigned job;
+};
+__global__ void __launch_bounds__(256) bb_ring_append(BbAppendParams q) {
+  const BbRing a = q.list[q.first + (int)blockIdx.x];
+  bool before;
+  const long long pos = bb_ring_pos(q.job, a.job0, q.olen, a.ring_len, &before);
+  if (a.ch < 0 || before) return;                                               // (workgroup-uniform) not attached / a block from before the attach
+  const float2* __restrict__ row = q.out + (size_t)a.ch * q.olen;
+  for (int m = (int)threadIdx.x; m < q.olen; m += (int)blockDim.x) {
+    long long i = pos + m; if (i >= a.ring_len) i -= a.ring_len;                // olen <= ring_len: at most one wrap
+    a.ring[i] = row[m];
   }
 }
 

@@ -135,6 +135,11 @@ inline int launch_welch(const ChanGeom& g, WelchParams q, const float2* tw, int 
   CHZ_LAUNCH(welch_sum, q.nslots, 256, 8 * sizeof(double), s, (q.segs > 0 ? (hipEvent_t) nullptr : e0), e1, q);
   return 0;
 }
+// the baseband rings of a bank's attached narrowband analysers list[first .. first + n)
+inline void launch_bb_append(BbAppendParams q, int n, hipStream_t s) {
+  if (n <= 0) return;
+  CHZ_LAUNCH(bb_ring_append, n, q.olen >= 256 ? 256 : 64, 0, s, (hipEvent_t) nullptr, (hipEvent_t) nullptr, q);
+}
 inline int launch_notch_fix(hipStream_t s, const NotchFixParams& p, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
   if (p.n <= 0) return 0;
   if (p.n > 1024) return -1;

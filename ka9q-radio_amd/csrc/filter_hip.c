@@ -56,6 +56,10 @@
 #pragma weak chz_welch_poll
 #pragma weak chz_welch_read_async
 #pragma weak chz_engine_info            /* used by ka9q_hip_spectrum() only */
+#pragma weak chz_bank_welch_create      /* ka9q_hip_spectrum_narrow(): -1 on an engine library without the narrowband analyser */
+#pragma weak chz_bank_welch_attach
+#pragma weak chz_bank_welch_configure
+#pragma weak chz_bank_welch_poll
 
 /* Environment: the shipped library reads the operator's variables only.  Tuning / A-B hooks of earlier rounds
    (KA9Q_HIP_WAKE, KA9Q_HIP_WAKE_SHARDS, KA9Q_HIP_BANK_CHANNELS, KA9Q_HIP_MINI, KA9Q_HIP_MINI_POOL) exist in -DCHZ_EXPERIMENTS builds only. */
@@ -183,6 +187,12 @@ struct mctx {
   int nwelch, welch_next;
   unsigned welch_epoch;             /* engines sh[0] has had: an analysis that spans a recovery gives up */
   pthread_mutex_t welch_lock;       /* one analysis at a time */
+  /* ka9q_hip_spectrum_narrow(): one analyser bank of one analyser per (slave, fft_n), attached to the slave's channel of its bank from
+     block job0 on; an entry whose slave has moved (device, bank, index) or whose bank was re-created is made afresh, with zero history */
+#define NB_CACHE 8
+  struct { struct filter_out *slave; int dev, cbank, idx, fft_n, id, max_bins, max_avg; unsigned job0; bool have_window; uint64_t window_fp; } nb[NB_CACHE];
+  int nnb, nb_next;
+  unsigned nb_epoch;                /* moves on when a recovery replaces the engines (the entries went with them) */
   unsigned welch_flag;              /* raised by the polls' stream behind the analysis in flight (futex word) */
   void *retired_mini;               /* an undecided small master became this engine in place: its old context (see create_input_impl) */
   int bank_cap0;                    /* channels a new bank starts with (KA9Q_HIP_BANK_CHANNELS, default 64; banks double as they fill) */
@@ -669,9 +679,9 @@ static int create_input_impl(struct filter_in *master, int const L, int const M,
   size_t const ring_bytes = page_round((size_t)ND * N * ssz);       /* src/filter.c:237,253 */
   void *ring = NULL;
   void *fd[ND] = {NULL, NULL, NULL, NULL};
+  float *zeros = NULL;              /* (in front of the first goto fail, which frees it) */
   for (int i = 0; i < ND; i++)
     if (chz_host_alloc(&fd[i], sizeof(float complex) * (size_t)bins) != 0) { fprintf(stderr, "create_filter_input: %s\n", chz_last_error()); goto fail; }
-  float *zeros = NULL;
   if (force_engine) {
     if (master->input_buffer == NULL || master->input_buffer_size != ring_bytes || (zeros = calloc((size_t)L, ssz)) == NULL) goto fail;
     ring = master->input_buffer;
@@ -873,6 +883,16 @@ done:;
   return 0;
 }
 
+/* forget the narrowband analysers of `slave` (NULL: everybody's); caller holds c->lock.  The next ka9q_hip_spectrum_narrow() starts afresh. */
+static void nb_drop(struct mctx *c, struct filter_out const *slave) {
+  for (int i = 0; i < c->nnb; ) {
+    if (slave != NULL && c->nb[i].slave != slave) { i++; continue; }
+    if (chz_welch_destroy) (void)chz_welch_destroy(c->sh[c->nb[i].dev].eng, c->nb[i].id);
+    c->nb[i] = c->nb[--c->nnb];
+  }
+  if (c->nb_next >= NB_CACHE) c->nb_next = 0;
+}
+
 int delete_filter_output(struct filter_out *slave) {
   if (slave == NULL) return -1;
   /* src/wfm.c:290-293 deletes its composite MASTER first and the three slaves after it (the reference's delete_filter_output never looks at the
@@ -887,6 +907,7 @@ int delete_filter_output(struct filter_out *slave) {
     struct mctx *c = MCTX(slave->master);
     struct sctx *sc = SCTX(slave);
     pthread_mutex_lock(&c->lock);
+    nb_drop(c, slave);
     stage_wrlock(c);
     struct shard *const sh = &c->sh[sc->dev];
     struct hbank *b = &sh->banks[sc->bank];
@@ -985,7 +1006,7 @@ static void recover_engine(struct mctx *c, struct filter_in *f, unsigned job) {
   for (int g = 0; g < c->nsh; g++) {
     struct shard *sh = &c->sh[g];
     chz_engine_destroy(sh->eng);
-    if (g == 0) { c->nwelch = 0; c->welch_epoch++; }      /* its welch banks went with it */
+    if (g == 0) { c->nwelch = 0; c->welch_epoch++; c->nnb = 0; c->nb_epoch++; }      /* its welch banks went with it (the narrowband ones of every device: all engines go here) */
     sh->eng = NULL;
     if (chz_engine_create(&sh->eng, f->ilen, f->impulse_length, f->in_type == REAL ? CHZ_REAL : CHZ_COMPLEX, sh->device, NULL, 0) != 0) {
       fprintf(stderr, "filter_hip: %s\n", chz_last_error());
@@ -1232,7 +1253,7 @@ int execute_filter_input(struct filter_in *const f) {
       }
       chz_bank_set_active(sh->eng, b->id, b->n);
       PROF_STAGE(c, job, 4, tst);
-      rc = chz_bank_execute(sh->eng, b->id, slot);
+      rc = chz_bank_execute(sh->eng, b->id, job);          /* the block NUMBER: the rings of attached narrowband analysers are placed by it */
       PROF_STAGE(c, job, 5, tst);
       if (rc == 0) rc = chz_bank_read_async(sh->eng, b->id, slot, 0, b->n, (float *)b->stage[slot]);
       if (rc == 0 && b->noise_on) rc = chz_bank_read_noise_async(sh->eng, b->id, slot, 0, b->n, b->stage_n0[slot]);
@@ -1342,7 +1363,7 @@ static void serve_misses(struct mctx *c, struct miss_req *list) {
       bool const ranged = cnt > MISS_BATCH && same_job && b->stage_job[slot] != UINT_MAX && hi <= b->stage_n[slot];
       if (ranged) {
         if (!wide) { stage_wrlock(c); wide = true; }
-        rc = chz_bank_execute_range(sh->eng, b->id, (unsigned)slot, lo, hi - lo);
+        rc = chz_bank_execute_range(sh->eng, b->id, b->stage_job[slot], lo, hi - lo);
         if (rc == 0) rc = chz_bank_read_async(sh->eng, b->id, slot, lo, hi - lo, (float *)((char *)b->stage[slot] + (size_t)lo * b->olen * bank_sample_bytes(b)));
         if (rc == 0 && b->noise_on) rc = chz_bank_read_noise_async(sh->eng, b->id, slot, lo, hi - lo, b->stage_n0[slot] + lo);
         /* what the image now holds for EVERY channel of the range: computed with the bank's current shifts, ISB flags and responses */
@@ -1358,7 +1379,8 @@ static void serve_misses(struct mctx *c, struct miss_req *list) {
         if (ranged) { r->rc = rc; r->ranged = true; }
         else {
           int const k = sc->idx;
-          rc = chz_bank_execute_range(sh->eng, b->id, (unsigned)slot, k, 1);
+          /* the block whose spectrum the slot holds (same slot: untuned banks compute the same either way; an analyser's ring takes the row for that block) */
+          rc = chz_bank_execute_range(sh->eng, b->id, b->stage_job[slot] != UINT_MAX ? b->stage_job[slot] : (unsigned)slot, k, 1);
           if (rc == 0) rc = chz_bank_read_async(sh->eng, b->id, slot, k, 1, (float *)((char *)b->stage[slot] + (size_t)k * b->olen * bank_sample_bytes(b)));
           if (rc == 0 && b->noise_on) rc = chz_bank_read_noise_async(sh->eng, b->id, slot, k, 1, b->stage_n0[slot] + k);
           r->rc = rc;
@@ -1562,6 +1584,7 @@ int filter_hip_enable_noise(struct filter_in *master, double samprate) {
   struct mctx *c = MCTX(master);
   int rc = 0;
   pthread_mutex_lock(&c->lock);
+  nb_drop(c, NULL);                 /* bank_warm() below runs the banks on block numbers 0..3: no ring may take those for blocks of the stream */
   stage_wrlock(c);
   c->noise_samprate = samprate;
   for (int g = 0; g < c->nsh; g++) for (int i = 0; i < c->sh[g].nbanks; i++) {
@@ -1653,6 +1676,97 @@ int ka9q_hip_spectrum(struct filter_in *master, int fft_n, const float *window, 
     while (__atomic_load_n(&c->welch_flag, __ATOMIC_ACQUIRE) == 0) futex_wait_u32(&c->welch_flag, 0);
     pthread_mutex_lock(&c->lock);
     bool const same = epoch == c->welch_epoch;
+    pthread_mutex_unlock(&c->lock);
+    if (same) { memcpy(bin_data, rows, sizeof(float) * (size_t)bin_count); if (minmax) { minmax[0] = mm[0]; minmax[1] = mm[1]; } rc = eff; }
+  }
+  free(rows);
+  pthread_mutex_unlock(&c->welch_lock);
+  return rc;
+unlock:
+  pthread_mutex_unlock(&c->lock);
+  pthread_mutex_unlock(&c->welch_lock);
+  return -1;
+}
+/* narrowband_poll() (src/spectrum.c:206-306) on the device, for a COMPLEX slave: fft_avg windowed segments of fft_n samples of the
+   slave's output, ending with the last sample of the block its last execute_filter_output() delivered, transformed, |X|^2 summed into
+   bin_data[] in the reference's order (include/chz_engine.h, chz_bank_welch_*).  The first call for a (slave, fft_n) attaches an
+   analyser to the slave's channel from the NEXT block the master issues on (it drains the device once); history before that is zeros,
+   like the reference's fresh ring (:142-144), so that first call reports zeros.  The drop-in's banks are untuned: this is the spectrum
+   BEFORE downconvert()'s fine rotation, narrowband_poll()'s own only where chan->filter.remainder is zero.  Synchronous.  Returns
+   fft_avg; -1 for an inline / mini master, a REAL slave, a slave more than ND blocks behind, bad arguments, or an engine library without the analyser. */
+int ka9q_hip_spectrum_narrow(struct filter_out *slave, int fft_n, const float *window, int bin_count, int fft_avg, double overlap,
+                             float *bin_data, double minmax[2]) {
+  if (!chz_bank_welch_create || !chz_bank_welch_attach || !chz_bank_welch_configure || !chz_bank_welch_poll || !chz_welch_destroy ||
+      !chz_welch_set_window || !chz_welch_read_async) return -1;
+  if (slave == NULL || slave->rev_plan == NULL || slave->master == NULL || slave->master->fwd_plan == NULL || is_mini_master(slave->master)) return -1;
+  if (*(const int *)(const void *)slave->rev_plan != CTX_SLAVE || slave->out_type != COMPLEX) return -1;
+  if (window == NULL || bin_data == NULL || fft_n < 1 || bin_count < 1 || bin_count > fft_n || fft_avg < 1 || !(overlap >= 0 && overlap < 1)) return -1;
+  struct filter_in *const master = slave->master;
+  struct mctx *c = MCTX(master);
+  struct sctx *sc = SCTX(slave);
+  uint64_t fp = 1469598103934665603ull;                    /* the window's fingerprint, as in ka9q_hip_spectrum() */
+  for (int i = 0; i < fft_n; i++) { uint32_t u; memcpy(&u, &window[i], sizeof u); fp = (fp ^ u) * 1099511628211ull; }
+  unsigned const job = slave->next_jobnum - 1u;            /* the block delivered last (this is the slave's own thread) */
+  int rc = -1, eff = -1;
+  float *rows = NULL;
+  double mm[2] = {0, 0};
+  bool polled = false;
+  pthread_mutex_lock(&c->welch_lock);
+  /* c->lock -- the lock every block is enqueued under -- is held to find or make the analyser and to ISSUE the work, never across the wait for the poll */
+  pthread_mutex_lock(&c->lock);
+  unsigned const epoch = c->nb_epoch;
+  struct hbank *const hb = &c->sh[sc->dev].banks[sc->bank];
+  chz_engine *const eng = c->sh[sc->dev].eng;
+  if (hb->real) goto unlock;
+  int k = -1;
+  for (int i = 0; i < c->nnb; i++) if (c->nb[i].slave == slave && c->nb[i].fft_n == fft_n) k = i;
+  int want_bins = bin_count, want_avg = fft_avg;
+  if (k >= 0 && (c->nb[k].dev != sc->dev || c->nb[k].cbank != hb->id || c->nb[k].idx != sc->idx || c->nb[k].max_bins < bin_count || c->nb[k].max_avg < fft_avg)) {
+    /* moved, or outgrown (a longer ring starts as zeros: include/chz_engine.h) */
+    if (c->nb[k].max_bins > want_bins) want_bins = c->nb[k].max_bins;
+    if (c->nb[k].max_avg > want_avg) want_avg = c->nb[k].max_avg;
+    (void)chz_welch_destroy(c->sh[c->nb[k].dev].eng, c->nb[k].id);
+    c->nb[k].fft_n = 0;
+  } else if (k < 0) {
+    if (c->nnb < NB_CACHE) k = c->nnb++;
+    else { k = c->nb_next; c->nb_next = (c->nb_next + 1) % NB_CACHE; (void)chz_welch_destroy(c->sh[c->nb[k].dev].eng, c->nb[k].id); }
+    c->nb[k].fft_n = 0;
+  }
+  if (c->nb[k].fft_n == 0) {
+    unsigned const job0 = __atomic_load_n(&master->next_jobnum, __ATOMIC_RELAXED);    /* the next block: the producer enqueues under c->lock */
+    int const nid = chz_bank_welch_create(eng, hb->id, fft_n, 1, want_bins, want_avg);
+    if (nid < 0 || chz_bank_welch_attach(eng, nid, 0, sc->idx, job0) != 0) {
+      if (nid >= 0) (void)chz_welch_destroy(eng, nid);
+      c->nb[k] = c->nb[--c->nnb];
+      goto unlock;
+    }
+    c->nb[k].slave = slave; c->nb[k].dev = sc->dev; c->nb[k].cbank = hb->id; c->nb[k].idx = sc->idx; c->nb[k].fft_n = fft_n; c->nb[k].id = nid;
+    c->nb[k].max_bins = want_bins; c->nb[k].max_avg = want_avg; c->nb[k].job0 = job0; c->nb[k].have_window = false;
+  }
+  int const id = c->nb[k].id;
+  if ((!c->nb[k].have_window || c->nb[k].window_fp != fp) && chz_welch_set_window(eng, id, 0, window) == 0) { c->nb[k].have_window = true; c->nb[k].window_fp = fp; }
+  if (c->nb[k].have_window && c->nb[k].window_fp == fp) eff = chz_bank_welch_configure(eng, id, 0, bin_count, fft_avg, overlap);
+  if (eff >= 1 && (int)(job - c->nb[k].job0) >= 0) {
+    rows = malloc(sizeof(float) * (size_t)c->nb[k].max_bins);
+    if (rows == NULL) eff = -1;
+    __atomic_store_n(&c->welch_flag, 0u, __ATOMIC_RELEASE);
+    if (eff >= 1) {
+      if (chz_bank_welch_poll(eng, id, 1, NULL, job) != 0) eff = -1;                 /* (a slave more than ND blocks behind: the ring has moved on) */
+      else if (chz_welch_read_async(eng, id, 0, 1, rows, mm) != 0 || chz_host_callback(eng, CHZ_SLOT_WELCH, welch_note, &c->welch_flag) != 0) {
+        chz_sync(eng);                                    /* something may be in flight towards rows / mm: drain before they go away */
+        eff = -1;
+      } else polled = true;
+    }
+  }
+  pthread_mutex_unlock(&c->lock);
+  if (eff >= 1 && !polled) {                              /* every sample of the window lies before the attach: the fresh ring's zeros */
+    memset(bin_data, 0, sizeof(float) * (size_t)bin_count);
+    if (minmax) { minmax[0] = 0; minmax[1] = 0; }
+    rc = eff;
+  } else if (polled) {
+    while (__atomic_load_n(&c->welch_flag, __ATOMIC_ACQUIRE) == 0) futex_wait_u32(&c->welch_flag, 0);
+    pthread_mutex_lock(&c->lock);
+    bool const same = epoch == c->nb_epoch;               /* a recovery replaced the engine meanwhile: its streams were drained, the result is void */
     pthread_mutex_unlock(&c->lock);
     if (same) { memcpy(bin_data, rows, sizeof(float) * (size_t)bin_count); if (minmax) { minmax[0] = mm[0]; minmax[1] = mm[1]; } rc = eff; }
   }

@@ -68,6 +68,7 @@ SYMBOLS = [
     "chz_comm_barrier", "chz_comm_allreduce_max", "chz_spectrum_broadcast", "chz_spectrum_exchange_rows", "chz_run_blocks_sharded",
     "chz_comm_create_local", "chz_spectrum_broadcast_local", "chz_set_option",
     "chz_welch_create", "chz_welch_destroy", "chz_welch_set_window", "chz_welch_configure", "chz_welch_poll", "chz_welch_read", "chz_welch_read_async",
+    "chz_bank_welch_create", "chz_bank_welch_attach", "chz_bank_welch_detach", "chz_bank_welch_configure", "chz_bank_welch_poll", "chz_bank_welch_steps",
 ]
 
 # the CHZ_* variables tests and scripts have always used to force a code path or arm a test hook: the shipped library does not read
@@ -176,6 +177,12 @@ def lib():
         L.chz_welch_poll.argtypes = [_vp, _i, _i, _vp, C.c_longlong]
         L.chz_welch_read.argtypes = [_vp, _i, _i, _i, _vp, _vp]
         L.chz_welch_read_async.argtypes = [_vp, _i, _i, _i, _vp, _vp]
+        L.chz_bank_welch_create.argtypes = [_vp, _i, _i, _i, _i, _i]
+        L.chz_bank_welch_attach.argtypes = [_vp, _i, _i, _i, _u]
+        L.chz_bank_welch_detach.argtypes = [_vp, _i, _i]
+        L.chz_bank_welch_configure.argtypes = [_vp, _i, _i, _i, _i, _d]
+        L.chz_bank_welch_poll.argtypes = [_vp, _i, _i, _vp, _u]
+        L.chz_bank_welch_steps.argtypes = [_i, _i, _d, _u, _u, _i, C.c_longlong, C.POINTER(C.c_longlong * 3)]
         _lib = L
     return _lib
 
@@ -513,15 +520,24 @@ class Bank:
         _check(lib().chz_bank_output_device(self.eng._h, self.id, slot, C.byref(p)))
         return p.value
 
+    def spectrum(self, fft_n, capacity, max_bins, max_avg):
+        """A bank of narrowband spectrum analysers (narrowband_poll(), src/spectrum.c:206-306) on the baseband of this bank's channels."""
+        return BankSpectrum(self, fft_n, capacity, max_bins, max_avg)
+
 
 class Welch:
     """chz_welch_*: `capacity` analysers sharing one fft_n; one poll serves any number of them."""
 
     def __init__(self, eng, fft_n, capacity, max_bins, max_avg):
+        self._setup(eng, fft_n, capacity, max_bins, max_avg, lib().chz_welch_create(eng._h, fft_n, capacity, max_bins, max_avg))
+
+    def _setup(self, eng, fft_n, capacity, max_bins, max_avg, bank_id):
+        """the state both kinds of bank share (read, set_window and close use nothing else)"""
         self.eng, self.fft_n, self.capacity, self.max_bins, self.max_avg = eng, fft_n, capacity, max_bins, max_avg
-        self.id = _check(lib().chz_welch_create(eng._h, fft_n, capacity, max_bins, max_avg))
+        self.id = _check(bank_id)
         self.bin_count = [0] * capacity
         self.fft_avg = [0] * capacity
+        self._polled = []
 
     def set_window(self, slot, window):
         w = np.ascontiguousarray(window, np.float32).reshape(-1)
@@ -558,6 +574,36 @@ class Welch:
         if self.id is not None and self.eng._h:
             _check(lib().chz_welch_destroy(self.eng._h, self.id))
         self.id = None
+
+
+class BankSpectrum(Welch):
+    """chz_bank_welch_*: `capacity` analysers sharing one fft_n, each attached to one channel of a COMPLEX-output bank whose rows
+    the device keeps in a ring per analyser; set_window, read and close are Welch's."""
+
+    def __init__(self, bank, fft_n, capacity, max_bins, max_avg):
+        self.bank = bank
+        self._setup(bank.eng, fft_n, capacity, max_bins, max_avg, lib().chz_bank_welch_create(bank.eng._h, bank.id, fft_n, capacity, max_bins, max_avg))
+
+    def attach(self, slot, channel, job0):
+        """Analyser `slot` follows `channel` from block job0 on; its history starts as zeros."""
+        _check(lib().chz_bank_welch_attach(self.eng._h, self.id, slot, channel, job0 & 0xFFFFFFFF))
+
+    def detach(self, slot):
+        _check(lib().chz_bank_welch_detach(self.eng._h, self.id, slot))
+
+    def configure(self, slot, bin_count, fft_avg, overlap):
+        eff = _check(lib().chz_bank_welch_configure(self.eng._h, self.id, slot, int(bin_count), int(fft_avg), float(overlap)))
+        self.bin_count[slot], self.fft_avg[slot] = int(bin_count), eff
+        return eff
+
+    def poll(self, slots=None, job=0):
+        """slots: analysers to serve (default: every configured one); the window ends just past block `job`.  Asynchronous; read() waits."""
+        if slots is None:
+            slots = [s for s in range(self.capacity) if self.fft_avg[s] > 0]
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        self._polled = [int(s) for s in sl]
+        if sl.shape[0]:
+            _check(lib().chz_bank_welch_poll(self.eng._h, self.id, sl.shape[0], sl.ctypes.data, job & 0xFFFFFFFF))
 
 
 COMM_ID_BYTES = 128
