@@ -481,7 +481,7 @@ int chz_engine_create(chz_engine** out, int L, int M, int in_type, int device, c
   if ((!plan_spec || !*plan_spec) && envspec && *envspec) plan_spec = envspec;
   if (!build_fwd_plan(N, in_type, plan_spec, e->plan)) {
     if (plan_spec && *plan_spec)
-      return fail(-3, "no transform plan for N=%d (spec '%s'): N must factor into the compiled axis lengths", N, plan_spec);
+      return fail(-3, "no transform plan for N=%d (spec '%s'): N must factor into the compiled axis lengths, and no pass may want more than 1024 threads or 160 KB of LDS", N, plan_spec);
     // any other length: chirp-z over the next planned complex length
     chz_engine::Blue* bl = new chz_engine::Blue();
     e->blue = bl;
@@ -509,6 +509,8 @@ int chz_engine_create(chz_engine** out, int L, int M, int in_type, int device, c
     q.desc = d;
   }
   const FwdPlan& tp = e->blue ? e->blue->zp : e->plan;         // the transform that is actually executed
+  if (fwd_lds_prepare(tp, !e->blue && in_type == CHZ_REAL))
+    return fail(-3, "the forward kernels of N=%d (%s) cannot have the LDS their tiles need", N, tp.desc.c_str());
   const int minblocks = (N + L - 1) / L + 1;
   if (ring_blocks < minblocks) ring_blocks = minblocks < 8 ? 8 : minblocks;
   e->ring_blocks = ring_blocks;

@@ -1133,7 +1133,7 @@ __global__ void __launch_bounds__(256, (R1 <= 15 && R2 <= 20) ? (EPI == 0 ? 6 : 
       // max over the channel's lanes (energies are >= 0: max of the lanes' maxima), a tree over the group: lane jl takes lane jl + d
       double tot = peak;
 #pragma unroll
-      for (int d = 16; d >= 1; d >>= 1) if (d < LPC) { const double o = __shfl_down(tot, (unsigned)d); if (jl + d < LPC && o > tot) tot = o; }
+      for (int d = 32; d >= 1; d >>= 1) if (d < LPC) { const double o = __shfl_down(tot, (unsigned)d); if (jl + d < LPC && o > tot) tot = o; }   // (d = 32: LPC is 40 or 48 at P = 1200 and 1920)
       if (live && jl == 0) p.agc_peak[ch] = tot;
     }
   }
@@ -1157,7 +1157,7 @@ __global__ void __launch_bounds__(256, (R1 <= 15 && R2 <= 20) ? (EPI == 0 ? 6 : 
   if (EPI && p.power != nullptr) {     // wave-uniform: every lane takes part in the shuffles
     double tot = part;                                       // (lanes outside the second layer hold 0)
 #pragma unroll
-    for (int d = 16; d >= 1; d >>= 1) if (d < LPC) { const double o = __shfl_down(tot, (unsigned)d); if (jl + d < LPC) tot += o; }
+    for (int d = 32; d >= 1; d >>= 1) if (d < LPC) { const double o = __shfl_down(tot, (unsigned)d); if (jl + d < LPC) tot += o; }   // (from 32: at P = 1920 the second layer fills lanes 0..39)
     if (live && jl == 0) p.power[ch] = tot / (double)p.olen;
   }
 }

@@ -81,6 +81,22 @@ inline int big_lds_prepare(const void* kern) {
   (void)kern; return 0;
 #endif
 }
+// The forward instantiations of a plan whose pass wants more than the default (the first pass of a REAL master with a long first axis:
+// 256x256 is 67,584 bytes, 400x400 128,640).  Called when a master is created, on the master's device -- the attribute belongs to the
+// (kernel, device) pair, so there is no process-wide "done" flag -- and not at all for a plan that stays below the default.
+// first_real: axis a runs fwd_first_real (a REAL master transformed directly), else fwd_cols.
+inline int fwd_lds_prepare(const FwdPlan& p, bool first_real) {
+  if (p.lds1 > CHZ_FWD_LDS_MAX || p.lds2 > CHZ_FWD_LDS_MAX || p.lds3 > CHZ_FWD_LDS_MAX) return -1;
+  int rc = 0;
+#define X(a, b) \
+  if (p.lds1 > CHZ_FWD_LDS_DEFAULT && p.ra.r1 == a && p.ra.r2 == b) \
+    rc |= first_real ? big_lds_prepare(reinterpret_cast<const void*>(fwd_first_real<a, b>)) : big_lds_prepare(reinterpret_cast<const void*>(fwd_cols<a, b>)); \
+  if (p.Nb > 1 && p.lds2 > CHZ_FWD_LDS_DEFAULT && p.rb.r1 == a && p.rb.r2 == b) rc |= big_lds_prepare(reinterpret_cast<const void*>(fwd_cols<a, b>)); \
+  if (p.lds3 > CHZ_FWD_LDS_DEFAULT && p.rc.r1 == a && p.rc.r2 == b) rc |= big_lds_prepare(reinterpret_cast<const void*>(fwd_rows<a, b>));
+  CHZ_FWD_MENU(X)
+#undef X
+  return rc ? -1 : 0;
+}
 // any P (prime factors up to 13) without a register-tiled kernel: one workgroup per channel (chan_any); needs the large-LDS attribute once
 inline int chan_any_prepare() {
 #if defined(__HIPCC__) && !defined(HIPEMU)

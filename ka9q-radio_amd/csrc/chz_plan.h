@@ -80,6 +80,8 @@ inline std::vector<f2> make_tw_sub(int r1, int r2, int sign) {
 }
 
 enum { CHZ_IN_COMPLEX = 1, CHZ_IN_REAL = 2 };   // enum filtertype values, src/filter.h:29-34
+#define CHZ_FWD_LDS_DEFAULT (64 * 1024)         // dynamic LDS a kernel gets without asking
+#define CHZ_FWD_LDS_MAX (160 * 1024)            // the LDS of a CU: no pass of a plan may want more
 
 struct FwdPlan {
   int N = 0, in_type = 0, bins = 0;
@@ -112,7 +114,8 @@ inline int pick_tile(int n, int want, int lo, int hi, int lanes_per_col, int max
   return best;
 }
 
-inline bool finish_fwd_plan(FwdPlan& p, int T1_over, int T2_over, int Ta_over) {
+// The scalar half of a plan: tile widths, grids, LDS sizes, spectrum layout and the description.  False: no launchable geometry.
+inline bool fwd_plan_geometry(FwdPlan& p, int T1_over, int T2_over, int Ta_over) {
   const bool real = p.in_type == CHZ_IN_REAL;
   p.inner = p.Nb * p.Nc;
   p.Ra = real ? p.Na / 2 + 1 : p.Na;
@@ -125,53 +128,24 @@ inline bool finish_fwd_plan(FwdPlan& p, int T1_over, int T2_over, int Ta_over) {
     p.T1 = T1_over > 0 ? T1_over : pick_tile(cols_p, 16, 8, 64, la, 1024);
     if (p.T1 <= 0 || cols_p % p.T1) return false;
     p.grid1 = cols_p / p.T1;
-    p.tw1_tile.resize((size_t)p.grid1 * p.Ra);
-    for (int tile = 0; tile < p.grid1; tile++)
-      for (int k = 0; k < p.Ra; k++)
-        p.tw1_tile[(size_t)tile * p.Ra + k] = root_of_unity((long long)k * 2 * tile * p.T1, p.N, -1);
-    p.tw1_col.resize((size_t)p.Ra * 2 * p.T1);
-    for (int k = 0; k < p.Ra; k++)
-      for (int cc = 0; cc < 2 * p.T1; cc++)   // 1/2 for even columns, 1/(2i) = -i/2 for odd ones
-        p.tw1_col[(size_t)k * 2 * p.T1 + cc] =
-            (cc & 1) ? root_of_unity((long long)k * cc, p.N, -1, 0.0, -0.5) : root_of_unity((long long)k * cc, p.N, -1, 0.5, 0.0);
   } else {
     p.T1 = T1_over > 0 ? T1_over : pick_tile(p.inner, 16, 8, 64, la, 1024);
     if (p.T1 <= 0 || p.inner % p.T1) return false;
     p.grid1 = p.inner / p.T1;
-    p.tw1_tile.resize((size_t)p.grid1 * p.Na);
-    for (int tile = 0; tile < p.grid1; tile++)
-      for (int k = 0; k < p.Na; k++)
-        p.tw1_tile[(size_t)tile * p.Na + k] = root_of_unity((long long)k * tile * p.T1, p.N, -1);
-    p.tw1_col.resize((size_t)p.Na * p.T1);
-    for (int k = 0; k < p.Na; k++)
-      for (int t = 0; t < p.T1; t++) p.tw1_col[(size_t)k * p.T1 + t] = root_of_unity((long long)k * t, p.N, -1);
   }
   p.padk1 = padk_for(p.ra.r2, p.T1);
   p.block1 = round_up(la * p.T1, 64);
   p.lds1 = sizeof(f2) * ((size_t)p.Na * p.T1 + (size_t)p.ra.r1 * p.padk1);
   if (real) p.lds1 += sizeof(f2) * (size_t)p.Na * p.T1;      // second region for the Hermitian split
-  p.tw_sub_a = make_tw_sub(p.ra.r1, p.ra.r2, -1);
   // ---- axis b
   if (p.Nb > 1) {
     const int lb = p.rb.r1 > p.rb.r2 ? p.rb.r1 : p.rb.r2;
     p.T2 = T2_over > 0 ? T2_over : pick_tile(p.Nc, 16, 8, 64, lb, 1024);
     if (p.T2 <= 0 || p.Nc % p.T2) return false;
-    const int tpr = p.Nc / p.T2;
-    p.grid2 = p.Ra * tpr;
+    p.grid2 = p.Ra * (p.Nc / p.T2);
     p.block2 = round_up(lb * p.T2, 64);
     p.padk2 = padk_for(p.rb.r2, p.T2);
     p.lds2 = sizeof(f2) * ((size_t)p.Nb * p.T2 + (size_t)p.rb.r1 * p.padk2);
-    const long long D = (long long)p.Nb * p.Nc;
-    p.tw2_tile.resize((size_t)tpr * p.Nb);
-    for (int ct = 0; ct < tpr; ct++)
-      for (int k = 0; k < p.Nb; k++) p.tw2_tile[(size_t)ct * p.Nb + k] = root_of_unity((long long)k * ct * p.T2, D, -1);
-    p.tw2_col.resize((size_t)p.Nb * p.T2);
-    for (int k = 0; k < p.Nb; k++)
-      for (int t = 0; t < p.T2; t++) p.tw2_col[(size_t)k * p.T2 + t] = root_of_unity((long long)k * t, D, -1);
-    p.tw2_full.resize((size_t)p.Nb * p.Nc);                 // W_D^(k*col): tile and column factor in one, rounded once
-    for (int k = 0; k < p.Nb; k++)
-      for (int c = 0; c < p.Nc; c++) p.tw2_full[(size_t)k * p.Nc + c] = root_of_unity((long long)k * c, D, -1);
-    p.tw_sub_b = make_tw_sub(p.rb.r1, p.rb.r2, -1);
   }
   // ---- last axis
   const int lc = p.rc.r1 > p.rc.r2 ? p.rc.r1 : p.rc.r2;
@@ -199,12 +173,63 @@ inline bool finish_fwd_plan(FwdPlan& p, int T1_over, int T2_over, int Ta_over) {
   p.grid3 = p.Nb * ((p.Ra + p.ka_shift + p.Ta - 1) / p.Ta);
   p.block3 = round_up(lc * p.Ta, 64);
   p.lds3 = sizeof(f2) * ((size_t)p.Nc * p.ld3 + (size_t)p.rc.r1 * p.padg3 + 8);
-  p.tw_sub_c = make_tw_sub(p.rc.r1, p.rc.r2, -1);
+  // a geometry the device cannot launch is no plan: the automatic search passes over it, an explicit one fails at create time.
+  // (Between CHZ_FWD_LDS_DEFAULT and CHZ_FWD_LDS_MAX the engine raises the kernel's limit once, fwd_lds_prepare in chz_launch.h:
+  // the first pass of a REAL master holds two regions of Na*T1 points, 128,640 bytes for 400x400.)
+  if (p.lds1 > CHZ_FWD_LDS_MAX || p.lds2 > CHZ_FWD_LDS_MAX || p.lds3 > CHZ_FWD_LDS_MAX) return false;
+  if (p.block1 > 1024 || p.block2 > 1024 || p.block3 > 1024) return false;
   char b[256];
   snprintf(b, sizeof b, "N=%d %s axes %dx%dx%d radices (%d,%d)(%d,%d)(%d,%d) tiles T1=%d T2=%d Ta=%d grids %d/%d/%d blocks %d/%d/%d spec pitch %d off %d",
            p.N, real ? "real" : "complex", p.Na, p.Nb, p.Nc, p.ra.r1, p.ra.r2, p.rb.r1, p.rb.r2, p.rc.r1, p.rc.r2,
            p.T1, p.T2, p.Ta, p.grid1, p.grid2, p.grid3, p.block1, p.block2, p.block3, p.spec_pitch, p.spec_off);
   p.desc = b;
+  return true;
+}
+// The twiddle tables of a geometry (float64-accurate, rounded once).  The automatic search builds them for the plan it keeps only.
+inline void fwd_plan_tables(FwdPlan& p) {
+  const bool real = p.in_type == CHZ_IN_REAL;
+  // ---- first axis
+  if (real) {
+    p.tw1_tile.resize((size_t)p.grid1 * p.Ra);
+    for (int tile = 0; tile < p.grid1; tile++)
+      for (int k = 0; k < p.Ra; k++)
+        p.tw1_tile[(size_t)tile * p.Ra + k] = root_of_unity((long long)k * 2 * tile * p.T1, p.N, -1);
+    p.tw1_col.resize((size_t)p.Ra * 2 * p.T1);
+    for (int k = 0; k < p.Ra; k++)
+      for (int cc = 0; cc < 2 * p.T1; cc++)   // 1/2 for even columns, 1/(2i) = -i/2 for odd ones
+        p.tw1_col[(size_t)k * 2 * p.T1 + cc] =
+            (cc & 1) ? root_of_unity((long long)k * cc, p.N, -1, 0.0, -0.5) : root_of_unity((long long)k * cc, p.N, -1, 0.5, 0.0);
+  } else {
+    p.tw1_tile.resize((size_t)p.grid1 * p.Na);
+    for (int tile = 0; tile < p.grid1; tile++)
+      for (int k = 0; k < p.Na; k++)
+        p.tw1_tile[(size_t)tile * p.Na + k] = root_of_unity((long long)k * tile * p.T1, p.N, -1);
+    p.tw1_col.resize((size_t)p.Na * p.T1);
+    for (int k = 0; k < p.Na; k++)
+      for (int t = 0; t < p.T1; t++) p.tw1_col[(size_t)k * p.T1 + t] = root_of_unity((long long)k * t, p.N, -1);
+  }
+  p.tw_sub_a = make_tw_sub(p.ra.r1, p.ra.r2, -1);
+  // ---- axis b
+  if (p.Nb > 1) {
+    const int tpr = p.Nc / p.T2;
+    const long long D = (long long)p.Nb * p.Nc;
+    p.tw2_tile.resize((size_t)tpr * p.Nb);
+    for (int ct = 0; ct < tpr; ct++)
+      for (int k = 0; k < p.Nb; k++) p.tw2_tile[(size_t)ct * p.Nb + k] = root_of_unity((long long)k * ct * p.T2, D, -1);
+    p.tw2_col.resize((size_t)p.Nb * p.T2);
+    for (int k = 0; k < p.Nb; k++)
+      for (int t = 0; t < p.T2; t++) p.tw2_col[(size_t)k * p.T2 + t] = root_of_unity((long long)k * t, D, -1);
+    p.tw2_full.resize((size_t)p.Nb * p.Nc);                 // W_D^(k*col): tile and column factor in one, rounded once
+    for (int k = 0; k < p.Nb; k++)
+      for (int c = 0; c < p.Nc; c++) p.tw2_full[(size_t)k * p.Nc + c] = root_of_unity((long long)k * c, D, -1);
+    p.tw_sub_b = make_tw_sub(p.rb.r1, p.rb.r2, -1);
+  }
+  // ---- last axis
+  p.tw_sub_c = make_tw_sub(p.rc.r1, p.rc.r2, -1);
+}
+inline bool finish_fwd_plan(FwdPlan& p, int T1_over, int T2_over, int Ta_over) {
+  if (!fwd_plan_geometry(p, T1_over, T2_over, Ta_over)) return false;
+  fwd_plan_tables(p);
   return true;
 }
 
@@ -253,7 +278,7 @@ inline bool build_fwd_plan(int N, int in_type, const char* spec, FwdPlan& out, d
       FwdPlan p; p.N = N; p.in_type = in_type; p.Na = a; p.Nb = b; p.Nc = c;
       fwd_menu_lookup(a, &p.ra); fwd_menu_lookup_c(c, &p.rc);
       if (b > 1) fwd_menu_lookup(b, &p.rb);
-      if (!finish_fwd_plan(p, 0, 0, 0)) continue;
+      if (!fwd_plan_geometry(p, 0, 0, 0)) continue;
       // cost model (fitted to scripts/plan_sweep.py runs on MI355X): every pass moves the whole
       // data set once; 128-byte aligned 16-column tiles run at copy speed and misaligned ones at
       // about half of it; a pass wants >= ~600 workgroups; long or lopsided butterflies cost VALU time
@@ -273,6 +298,7 @@ inline bool build_fwd_plan(int N, int in_type, const char* spec, FwdPlan& out, d
     }
   }
   if (!found) return false;
+  fwd_plan_tables(bestp);
   out = bestp;
   if (score_out) *score_out = best;
   return true;

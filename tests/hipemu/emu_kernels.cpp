@@ -108,6 +108,13 @@ int emu_plan_exists(int N, int in_type, char* desc, int len) {
   if (desc && len > 0) { strncpy(desc, p.desc.c_str(), (size_t)len - 1); desc[len - 1] = 0; }
   return 1;
 }
+// dynamic LDS (bytes) the three passes of a plan ask for: out3 = lds1, lds2 (0 for a two-axis plan), lds3; spec "" = the automatic plan
+int emu_plan_lds(int N, int in_type, const char* spec, long* out3) {
+  FwdPlan p;
+  if (!build_fwd_plan(N, in_type, spec ? spec : "", p)) return 0;
+  out3[0] = (long)p.lds1; out3[1] = (long)p.lds2; out3[2] = (long)p.lds3;
+  return 1;
+}
 // the division-free storage index of chan_ifft against the plain definition, for EVERY bin of a master: returns the first
 // disagreeing bin or -1; -2 if chan_layout refuses the layout
 long emu_spec_index_check(int na, int pitch, int off, long bins) {
