@@ -388,6 +388,31 @@ int chz_mini_set_response(chz_mini *m, int inst, const float *resp);            
 int chz_mini_execute(chz_mini *m, int n, const int *inst, const float *const *win, const int *shift, const unsigned char *isb,
                      float *const *out);
 
+/* ---- pools of small REAL inline masters with decimating slaves: wfm's composite master (src/wfm.c:70-89: L 7680, M 7681, a REAL
+ * and two COMPLEX slaves of olen 960), stereod (src/stereod.c:383-401), rdsd (src/rdsd.c:395-406), packetd (src/packetd.c:493-495),
+ * ctcss (src/ctcss.c:269-281).  A pool holds every instance of ONE geometry: (L, M, the slave list of (olen, out_type)); an instance
+ * is one master with all its slaves.  One launch serves every request that is due, one workgroup each, everything in LDS: the N real
+ * samples as an N/2-point packed transform and a Hermitian split, then per selected slave the gather x response of
+ * src/filter.c:803-911 (negative shifts, bins outside the master, ISB, the zeroed Nyquist bin), a P_s-point backward transform
+ * (P_s = N olen_s / L) and the last olen_s samples.  Stateless like chz_mini_*: a request carries its whole N-sample window.
+ * Limits, refused at chz_rmini_create and nowhere else: N even, 16 <= N <= 16384, N/2 without a prime factor above 13; 1 to 4
+ * slaves, each with P_s an integer, 8 <= P_s <= N, no prime factor above 13, even for a REAL slave; and
+ * 8 * max(N, N/2 + 1 + 2 max P_s) bytes of LDS within the 160 KB of a workgroup. */
+typedef struct chz_rmini chz_rmini;
+int chz_rmini_create(chz_rmini **out, int L, int M, int nslaves, const int *olen, const int *out_type, int capacity, int device);
+void chz_rmini_destroy(chz_rmini *m);
+int chz_rmini_check(int L, int M, int nslaves, const int *olen, const int *out_type);   /* would chz_rmini_create take this geometry? 0, or < 0 and chz_last_error(); touches no device */
+int chz_rmini_capacity(const chz_rmini *m);
+int chz_rmini_add(chz_rmini *m);                                                /* -> instance index */
+int chz_rmini_release(chz_rmini *m, int inst);
+int chz_rmini_set_response(chz_rmini *m, int inst, int slave, const float *resp);   /* P_s complex, as set_filter leaves it (a REAL slave's P_s/2 + 1 bins first) */
+/* n requests, one H2D, ONE launch and one D2H per chunk of `capacity`: instance inst[i], window win[i] (N floats on the host), per
+ * slave s the shift shift[i*nslaves+s] (NULL = 0) and ISB flag isb[i*nslaves+s] (NULL = off); mask[i] selects the slaves to run
+ * (bit s; NULL = all); out[i*nslaves+s] receives olen_s complex or float samples, may be NULL, and stays untouched for a slave the
+ * mask leaves out.  An instance may appear several times.  Synchronous, thread-safe. */
+int chz_rmini_execute(chz_rmini *m, int n, const int *inst, const float *const *win, const int *shift, const unsigned char *mask,
+                      const unsigned char *isb, float *const *out);
+
 /* ---- Welch power spectra of the raw input: radiod's wideband spectrum analyser (wideband_poll(), src/spectrum.c:308-522) on the
  * samples the engine's input ring holds (float REAL, float COMPLEX or the int16 of chz_input_write_i16).  A bank holds `capacity`
  * analysers sharing one fft_n (= lrint(samprate / rbw): any length from 8 to 2^20 points; one with a prime factor above 13 runs as

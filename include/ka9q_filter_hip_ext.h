@@ -65,6 +65,24 @@ int ka9q_hip_spectrum(struct filter_in *master, int fft_n, const float *window, 
  * library without the analyser. */
 int ka9q_hip_spectrum_narrow(struct filter_out *slave, int fft_n, const float *window, int bin_count, int fft_avg, double overlap,
                              float *bin_data, double minmax[2]);
+/* Pools of small REAL inline masters (default off; process-wide; affects masters created afterwards).  wfm's composite master
+ * (src/wfm.c:70-89), stereod, rdsd, packetd and ctcss keep a REAL master of a few thousand points per channel or session with one to
+ * three decimating slaves and run it inline; each is a full engine by default.  With the option on, a REAL master with an even
+ * N = L + M - 1 <= 16384 starts as host state only, its COMPLEX / REAL slaves register as they are created, and at the first
+ * execute_filter_output() it joins a pool shared by every master of its geometry (chz_rmini_*, include/chz_engine.h): one kernel
+ * launch serves every thread that is due, and one request computes all slaves of its master, so that the siblings' calls for the
+ * same block and shift are served from the host.  All slaves must exist before the master's first block; one the pool cannot serve (a
+ * fifth slave, a block size with a prime factor above 13), or a first block with no slave at all, makes the master an engine in
+ * place.  A pooled master is run INLINE whatever N_worker_threads says (master->perform_inline is set to true, as wfm, stereod, rdsd,
+ * packetd and ctcss set it themselves): execute_filter_input() only book-keeps and the work is done in the slaves' calls; a process
+ * that needs such a master's forward transform to run asynchronously leaves the option off.
+ * Returns 1 if such masters will be pooled from now on, 0 if not (switched off, or an engine library without the pools). */
+int ka9q_hip_pool_real_masters(int on);
+/* engines the drop-in has created in this process so far (one per master and device; pooled inline masters create none) */
+int ka9q_hip_engines_created(void);
+/* pools of REAL inline masters that exist in this process; instances (may be NULL) receives how many of their instances are taken
+   right now -- one per pooled master that still has its master or a slave alive */
+int ka9q_hip_real_master_pools(int *instances);
 #ifdef __cplusplus
 }
 #endif

@@ -2219,4 +2219,5 @@ int chz_run_blocks(chz_engine* e, unsigned job0, int nblocks, int mode, int inst
 
 #include "chz_comm.inc"
 #include "chz_mini.inc"
+#include "chz_rmini.inc"
 #include "chz_welch.inc"

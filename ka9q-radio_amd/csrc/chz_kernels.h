@@ -3405,6 +3405,122 @@ __global__ void __launch_bounds__(256) mini_ovs(MiniParams p) {
 }
 
 // ------------------------------------------------------------------------------
+// Small REAL inline masters with decimating slaves (wfm's composite master, src/wfm.c:70-89: L 7680, M 7681 with a REAL
+// and two COMPLEX slaves of olen 960; stereod, rdsd, packetd and ctcss keep the like).  One workgroup per request,
+// everything in LDS, stateless like mini_ovs: a request carries its whole N-sample REAL window.
+//   forward:  the N real samples travel as N/2 complex ones through an N/2-point Stockham transform (mini_fft, buffers
+//             A = lds[0, H) and B = lds[H, 2H), H = N/2); the Hermitian split (as welch_seg's, twiddles e^{-2 pi i k / N} from a
+//             float64-rounded table) leaves the master's H + 1 bins in S = lds[0, H]: in place when the transform ended in A
+//             (bin H lands on B[0], free by then), from B into A otherwise.  One thread owns the pair (k, H - k), so nothing
+//             is read after it was overwritten.
+//   slaves:   for every slave the request's mask selects, one after the other: gather x response into Y = lds[H+1, H+1+P)
+//             with the rules of chan_ifft / chan_c2r / chan_any for a REAL master (src/filter.c:803-892: negative shifts read
+//             downwards, conjugated; bins outside the master are zero), ISB unpacking and the zeroed Nyquist bin (:895-911),
+//             a P-point backward transform between Y and W = Y + P (a REAL slave as the Hermitian extension of its P/2 + 1
+//             bins, as chan_any does it), the last olen samples leave.  S is never written again, so every slave reads the
+//             same master spectrum.
+// LDS: 8 * max(2H, H + 1 + 2 max P) bytes -- wfm: 2 x 7680 points forward (122,880 B), then 7681 bins + 2 x 1920 (92,168 B).
+// Threads per workgroup (host, chz_rmini_create): H/4 rounded up to whole wavefronts, one radix-4 butterfly per thread and
+// stage; at most 256 while the geometry's LDS lets four workgroups share a CU (<= 40 KB), at most 1024 beyond, where a
+// CU holds one to three workgroups and the workgroup itself has to keep the four SIMDs busy between barriers.
+// ------------------------------------------------------------------------------
+#define CHZ_RMINI_MAX_SLAVES 4
+struct RminiReq { ChanDesc d[CHZ_RMINI_MAX_SLAVES]; int isb[CHZ_RMINI_MAX_SLAVES]; int mask; int pad[3]; };   // d[s].row = response row, d[s].shift = shift
+struct RminiSlave {
+  MiniParams m;           // m.N = P, m.tw = [P] e^{-2 pi i k / P}, m.resp = [rows][P], m.olen; in / out / req unused
+  int real_out;           // REAL slave: olen floats leave, the response holds P/2 + 1 bins
+  int out_off;            // first float of this slave's samples in a request's output row (even)
+};
+struct RminiParams {
+  const float* in;        // [nreq][N] windows
+  float* out;             // [nreq][out_stride] floats
+  const RminiReq* req;    // [nreq]
+  const float2* tw_split; // [N/2 + 1] e^{-2 pi i k / N}
+  MiniParams fwd;         // the N/2-point forward transform: fwd.N = N/2, fwd.tw = [N/2]
+  int N, nslaves, out_stride;
+  RminiSlave s[CHZ_RMINI_MAX_SLAVES];
+};
+
+__global__ void __launch_bounds__(1024) rmini_ovs(RminiParams p) {
+  HIP_DYNAMIC_SHARED(float2, lds)
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int H = p.N / 2;
+  float2* A = lds;
+  float2* B = lds + H;
+  const RminiReq* __restrict__ rq = p.req + blockIdx.x;
+  const float2* __restrict__ win = reinterpret_cast<const float2*>(p.in + (size_t)blockIdx.x * p.N);
+  for (int i = tid; i < H; i += nthr) A[i] = win[i];                       // the pair (2i, 2i+1)
+  __syncthreads();
+  const float2* Z = mini_fft<-1>(A, B, p.fwd, tid, nthr);
+  float2* S = lds;
+  for (int k = tid; 2 * k <= H; k += nthr) {                               // X_k = (Z_k + conj Z_{H-k})/2 - i/2 W^k (Z_k - conj Z_{H-k})
+    const int kk = H - k;
+    const float2 zk = Z[k], zm = Z[k == 0 ? 0 : kk];
+    const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
+    const float2 o = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
+    const float2 t = cmul(o, p.tw_split[k]);
+    const float2 u = cmul(make_float2(o.x, -o.y), p.tw_split[kk]);         // bin H - k: conj(e), conj(o)
+    S[k] = make_float2(e.x + t.x, e.y + t.y);
+    if (kk != k) S[kk] = make_float2(e.x + u.x, u.y - e.y);
+  }
+  __syncthreads();
+  const int mask = rq->mask;
+  const int m_bins = H + 1;
+  float2* Y = lds + H + 1;
+  for (int s = 0; s < p.nslaves; s++) {                                    // (workgroup-uniform control flow throughout)
+    if (!((mask >> s) & 1)) continue;
+    const MiniParams& sm = p.s[s].m;
+    const int P = sm.N;
+    const ChanDesc d = rq->d[s];
+    const float2* __restrict__ Hr = sm.resp + (size_t)d.row * P;
+    float2* W = Y + P;
+    if (!p.s[s].real_out) {
+      for (int i = tid; i < P; i += nthr) {
+        int t = i - (P + 1) / 2; if (t < 0) t += P;                        // rank from the most negative bin
+        const int u = t - d.t0;
+        const bool ok = (u >= 0) && (u < d.cnt);
+        const int src = d.src0 + d.dir * u;
+        float2 v = make_float2(0.f, 0.f);
+        if (ok) { v = S[src]; if (d.conj) v.y = -v.y; v = cmul(v, Hr[i]); }
+        Y[i] = v;
+      }
+      __syncthreads();
+      if (rq->isb[s]) {                                                    // src/filter.c:895-909: pairs p = 1 .. s_bins/2 - 1 (an odd P leaves its innermost pair alone)
+        for (int q = tid; q < P / 2; q += nthr) {
+          if (q == 0) { Y[0] = make_float2(0.f, 0.f); continue; }
+          const float2 pos = Y[q], neg = Y[P - q];
+          Y[q] = make_float2(pos.x + neg.x, pos.y - neg.y);                // pos + conj(neg)
+          Y[P - q] = make_float2(neg.x - pos.x, neg.y + pos.y);            // neg - conj(pos)
+        }
+        __syncthreads();
+      }
+      if (tid == 0) Y[(P + 1) / 2] = make_float2(0.f, 0.f);                // :911 comes after the unpack
+    } else {
+      const int SB = P / 2 + 1;
+      for (int i = tid; i < P; i += nthr) {
+        const int k = i <= P / 2 ? i : P - i;                              // the slave bin this entry of the Hermitian extension comes from
+        const int mi = k + d.shift;
+        const bool ok = mi >= 0 && mi < m_bins && k != (SB + 1) / 2;       // :808, :911
+        float2 x = make_float2(0.f, 0.f);
+        if (ok) {
+          x = cmul(S[mi], Hr[k]);
+          if (k == 0 || 2 * k == P) x.y = 0.f;                             // c2r ignores these imaginary parts
+          if (i > P / 2) x.y = -x.y;
+        }
+        Y[i] = x;
+      }
+    }
+    __syncthreads();
+    const float2* T = mini_fft<+1>(Y, W, sm, tid, nthr);
+    const int drop = P - sm.olen;
+    float* __restrict__ o = p.out + (size_t)blockIdx.x * p.out_stride + p.s[s].out_off;
+    if (p.s[s].real_out) { for (int n = tid; n < sm.olen; n += nthr) o[n] = T[drop + n].x; }
+    else { float2* __restrict__ oc = reinterpret_cast<float2*>(o); for (int n = tid; n < sm.olen; n += nthr) oc[n] = T[drop + n]; }
+    __syncthreads();                                                       // the next slave overwrites both buffers
+  }
+}
+
+// ------------------------------------------------------------------------------
 // K3+K4 for ANY P without a prime factor above 13 -- the sizes the register-tiled chan_ifft / chan_c2r menu does not hold
 // (wfm's 384 kHz channel on a 20 ms block with overlap 5 is P = 9600, src/wfm.c:37-39; odd sample rates).  One workgroup
 // per channel: the gather x response of src/filter.c:728-911 lands in LDS in FFT order (COMPLEX or REAL output, ISB

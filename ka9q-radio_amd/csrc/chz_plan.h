@@ -435,4 +435,45 @@ inline bool mini_factor(int N, int* radix, int* nstages) {
   return n == 1;
 }
 
+
+// ---- pooled small REAL masters (rmini_ovs): what a master of N points with slaves of P_s points asks of a workgroup -------------
+// LDS: two N/2-point buffers for the forward transform, then the N/2 + 1 bins plus two buffers of the largest slave.  Threads: N/8
+// rounded up to whole wavefronts, at most 256 while four workgroups share a CU (<= 40 KB of LDS), at most 1024 beyond (see rmini_ovs).
+#define CHZ_RMINI_LDS_MAX (160 * 1024)
+inline void rmini_launch_geom(int N, int maxP, size_t* lds, int* threads) {
+  const size_t H = (size_t)N / 2;
+  const size_t pts = 2 * H > H + 1 + 2 * (size_t)maxP ? 2 * H : H + 1 + 2 * (size_t)maxP;
+  *lds = sizeof(f2) * pts;
+  const int q = ((int)H / 4 + 63) / 64 * 64, top = *lds <= 40 * 1024 ? 256 : 1024;
+  *threads = q < 64 ? 64 : (q > top ? top : q);
+}
+// chz_rmini_create's limits, 0 or the first one that is broken (why: a message for fail()); P[s] receives N olen_s / L
+inline int rmini_check_geom(int L, int M, int nslaves, const int* olen, const int* out_type, int* P, char* why, size_t why_len) {
+  int rdx[CHZ_MINI_MAX_STAGES], nst = 0;
+  if (L < 1 || M < 1) { snprintf(why, why_len, "bad REAL mini-master geometry"); return -1; }
+  if (nslaves < 1 || nslaves > 4 || !olen || !out_type) { snprintf(why, why_len, "a pooled REAL master carries 1 to 4 slaves (got %d)", nslaves); return -3; }
+  const long long Nl = (long long)L + M - 1;
+  if (Nl & 1) { snprintf(why, why_len, "pooled REAL masters need an even N (got %lld): the forward transform packs sample pairs", Nl); return -3; }
+  if (Nl < 16 || Nl > 16384) { snprintf(why, why_len, "pooled REAL masters cover 16 <= N <= 16384 (got %lld); larger masters are engines", Nl); return -3; }
+  const int N = (int)Nl;
+  if (!mini_factor(N / 2, rdx, &nst)) { snprintf(why, why_len, "N/2=%d has a prime factor above 13: no pooled REAL master transform", N / 2); return -3; }
+  int maxP = 0;
+  for (int s = 0; s < nslaves; s++) {
+    if (out_type[s] != CHZ_IN_REAL && out_type[s] != CHZ_IN_COMPLEX) { snprintf(why, why_len, "slave %d: output type %d is neither REAL nor COMPLEX", s, out_type[s]); return -3; }
+    if (olen[s] < 1 || olen[s] > L) { snprintf(why, why_len, "slave %d: olen %d outside 1..L=%d", s, olen[s], L); return -3; }
+    const long long num = (long long)N * olen[s];
+    if (num % L) { snprintf(why, why_len, "slave %d: N*olen/L = %d*%d/%d is not an integer", s, N, olen[s], L); return -3; }
+    const int Ps = (int)(num / L);
+    if (Ps < 8 || Ps > N) { snprintf(why, why_len, "slave %d: P=%d outside 8..N=%d", s, Ps, N); return -3; }
+    if (out_type[s] == CHZ_IN_REAL && (Ps & 1)) { snprintf(why, why_len, "slave %d: a REAL slave needs an even P (got %d)", s, Ps); return -3; }
+    if (!mini_factor(Ps, rdx, &nst)) { snprintf(why, why_len, "slave %d: P=%d has a prime factor above 13", s, Ps); return -3; }
+    if (P) P[s] = Ps;
+    if (Ps > maxP) maxP = Ps;
+  }
+  size_t lds = 0; int thr = 0;
+  rmini_launch_geom(N, maxP, &lds, &thr);
+  if (lds > CHZ_RMINI_LDS_MAX) { snprintf(why, why_len, "N=%d with a %d-point slave needs %zu bytes of LDS per workgroup, more than the 160 KB there are", N, maxP, lds); return -3; }
+  return 0;
+}
+
 }  // namespace chz

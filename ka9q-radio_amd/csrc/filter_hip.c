@@ -60,6 +60,15 @@
 #pragma weak chz_bank_welch_attach
 #pragma weak chz_bank_welch_configure
 #pragma weak chz_bank_welch_poll
+/* likewise the pools of small REAL masters: without them ka9q_hip_pool_real_masters() changes nothing and such a master is an engine */
+#pragma weak chz_rmini_create
+#pragma weak chz_rmini_destroy
+#pragma weak chz_rmini_check
+#pragma weak chz_rmini_capacity
+#pragma weak chz_rmini_add
+#pragma weak chz_rmini_release
+#pragma weak chz_rmini_set_response
+#pragma weak chz_rmini_execute
 
 /* Environment: the shipped library reads the operator's variables only.  Tuning / A-B hooks of earlier rounds
    (KA9Q_HIP_WAKE, KA9Q_HIP_WAKE_SHARDS, KA9Q_HIP_BANK_CHANNELS, KA9Q_HIP_MINI, KA9Q_HIP_MINI_POOL) exist in -DCHZ_EXPERIMENTS builds only. */
@@ -535,6 +544,7 @@ static void mctx_free(struct mctx *c) {          /* host side (and the communica
     for (int i = 0; i < c->sh[g].nbanks; i++) bank_free_host(&c->sh[g].banks[i]);
     free(c->sh[g].banks);
   }
+  if (c->retired_mini && ((struct minictx *)c->retired_mini)->rs) rm_unref(((struct minictx *)c->retired_mini)->rs);
   free(c->retired_mini);
   pthread_mutex_destroy(&c->lock);
   pthread_mutex_destroy(&c->welch_lock);
@@ -602,6 +612,8 @@ static void engines_warm(struct mctx *c, struct filter_in *f, const float *zeros
 }
 
 static int create_input_impl(struct filter_in *master, int L, int M, enum filtertype in_type, bool force_engine);
+static int rmini_finish_conversion(struct filter_in *master);
+static int Engines_created;         /* ka9q_hip_engines_created() */
 int create_filter_input(struct filter_in *master, int const L, int const M, enum filtertype const in_type) {
   return create_input_impl(master, L, M, in_type, false);
 }
@@ -628,7 +640,7 @@ static int create_input_impl(struct filter_in *master, int const L, int const M,
     for (int i = 0; i < ND; i++) { chz_host_free(master->fdomain[i]); master->fdomain[i] = NULL; }
     ring_unmap(&master->input_buffer, master->input_buffer_size);
   }
-  if (!force_engine && mini_wanted(L, M, in_type)) return mini_create_input(master, L, M);   /* radiod's filter2 and its like */
+  if (!force_engine && (mini_wanted(L, M, in_type) || rmini_wanted(L, M, in_type))) return mini_create_input(master, L, M, in_type);   /* radiod's filter2 and its like; wfm's composite master and its like */
   struct mctx *c = calloc(1, sizeof *c);
   if (!c) return -1;
   c->kind = CTX_ENGINE;
@@ -641,6 +653,7 @@ static int create_input_impl(struct filter_in *master, int const L, int const M,
       free(c);
       return -1;
     }
+  __atomic_fetch_add(&Engines_created, c->nsh, __ATOMIC_RELAXED);
   c->master = master;
   { const char *ex = getenv("KA9Q_HIP_EXCHANGE");
     if (ex && strcmp(ex, "broadcast") == 0) c->bcast = true;
@@ -731,6 +744,7 @@ static int create_input_impl(struct filter_in *master, int const L, int const M,
     free(zeros);
     c->retired_mini = old_mini;            /* another thread may be looking at its kind word this instant (is_mini_master): it goes with the context, at delete */
     for (int i = 0; i < ND; i++) { free(old_fd[i]); futex_wake_all(&master->completed_jobs[i]); }      /* block clocks asleep on the old words look again */
+    /* (a pooled REAL master's registered slaves follow once the caller has let go of filter_mutex: rmini_finish_conversion) */
   }
   return 0;
 
@@ -780,6 +794,108 @@ int delete_filter_input(struct filter_in *master) {
   return 0;
 }
 
+/* a COMPLEX or REAL slave joins its engine master: host buffers, a place in a bank of its geometry on one of the master's devices.
+   keep_buffers: the slave was registered on a pooled REAL master that is becoming an engine and already owns its buffers
+   (rmini_finish_conversion); every other caller passes false and gets what create_filter_output always did. */
+static int engine_attach_output(struct filter_out *slave, struct filter_in *master, int len, enum filtertype out_type, bool keep_buffers) {
+  struct mctx *c = MCTX(master);
+  bool const real = out_type == REAL;
+  slave->bins = real ? slave->points / 2 + 1 : slave->points;    /* src/filter.c:346,374 */
+  if (!keep_buffers) slave->fdomain = lmalloc(sizeof(float complex) * (size_t)slave->bins);
+  struct sctx *sc = calloc(1, sizeof *sc);
+  if (sc) sc->kind = CTX_SLAVE;
+  if (keep_buffers) {
+    /* (fdomain, output_buffer and output stay as rmini_create_output made them: the same sizes and offsets as below) */
+  } else if (real) {
+    slave->output_buffer.r = lmalloc(sizeof(float) * (size_t)slave->points);
+    if (slave->output_buffer.r) { memset(slave->output_buffer.r, 0, sizeof(float) * (size_t)slave->points); slave->output.r = slave->output_buffer.r + slave->points - len; }   /* src/filter.c:385 */
+  } else {
+    slave->output_buffer.c = lmalloc(sizeof(float complex) * (size_t)slave->points);
+    if (slave->output_buffer.c) { memset(slave->output_buffer.c, 0, sizeof(float complex) * (size_t)slave->points); slave->output.c = slave->output_buffer.c + slave->bins - len; }  /* src/filter.c:357 */
+  }
+  if (!slave->fdomain || (!slave->output_buffer.c && !slave->output_buffer.r) || !sc) { FREE(slave->fdomain); FREE(slave->output_buffer.c); FREE(slave->output_buffer.r); free(sc); return -1; }
+  pthread_mutex_lock(&c->lock);
+  stage_wrlock(c);
+  /* which device: the first one that still has room in its share of shard_channels slaves (creation order fills device 0, then 1, ...:
+     contiguous blocks); with every share full, the one with the fewest slaves */
+  int dv = 0;
+  for (int g = 0; g < c->nsh; g++) if (c->sh[g].nslaves < c->shard_channels) { dv = g; goto chosen; }
+  for (int g = 1; g < c->nsh; g++) if (c->sh[g].nslaves < c->sh[dv].nslaves) dv = g;
+chosen:;
+  struct shard *const sh = &c->sh[dv];
+  int bi = bank_for(c, sh, slave->points, len, real);
+  if (bi < 0) {
+    stage_wrunlock(c);
+    pthread_mutex_unlock(&c->lock);
+    fprintf(stderr, "create_filter_output: no device kernel for P=%d\n", slave->points);
+    FREE(slave->fdomain); FREE(slave->output_buffer.c); FREE(slave->output_buffer.r); free(sc);
+    return -1;
+  }
+  struct hbank *b = &sh->banks[bi];
+  sc->dev = dv; sc->bank = bi; sc->idx = b->n; sc->epoch = 1; sc->n0 = NAN;
+  sc->shard = c->next_shard++ % c->wshards;
+  b->slaves[b->n] = slave; b->shift[b->n] = 0;
+  /* the device row must hold the descriptor of the shift the host believes it holds: a channel that only ever asks for shift 0
+     (the centre channel of a complex front end) would otherwise never send one and read an empty row */
+  if (chz_bank_set_shifts(sh->eng, b->id, b->n, 1, &b->shift[b->n]) != 0) {
+    stage_wrunlock(c);
+    pthread_mutex_unlock(&c->lock);
+    fprintf(stderr, "create_filter_output: %s\n", chz_last_error());
+    FREE(slave->fdomain); FREE(slave->output_buffer.c); FREE(slave->output_buffer.r); free(sc);
+    return -1;
+  }
+  if (!real && master->in_type == COMPLEX) {
+    /* likewise the beam form at this index (a reused index may still hold an earlier occupant's; radio.c sets out.beam BEFORE the demodulator creates
+       the filter output, src/radio.c:938-940, and create_filter_output has just reset the weights, src/filter.c:341) */
+    unsigned char const on = slave->beam ? 1 : 0;
+    if (b->beam_on[b->n] != on || on) {
+      double const ab[4] = {creal(slave->alpha), cimag(slave->alpha), creal(slave->beta), cimag(slave->beta)};
+      b->beam_on[b->n] = on; memcpy(b->beam_ab + 4 * b->n, ab, sizeof ab);
+      chz_bank_set_beam(sh->eng, b->id, b->n, 1, ab, &on);
+    }
+  }
+  for (int s = 0; s < ND; s++) b->stage_epoch[s][b->n] = 0;
+  b->n++; sh->nslaves++;
+  slave->rev_plan = (fftwf_plan)(void *)sc;
+  sync_notches(c, master);               /* radio.c installs the list right after create_filter_input (src/radio.c:601-620): uploaded before block 0, not by it */
+  stage_wrunlock(c);
+  pthread_mutex_unlock(&c->lock);
+  return 0;
+}
+/* the response set_filter left on the host goes to the slave's bank row */
+static int engine_upload_response(struct filter_out *slave) {
+  struct mctx *c = MCTX(slave->master);
+  struct sctx *sc = SCTX(slave);
+  pthread_mutex_lock(&c->lock);
+  stage_wrlock(c);
+  sc->epoch++;
+  stage_wrunlock(c);
+  pthread_mutex_lock(&slave->response_mutex);                      /* (inside c->lock, as in delete_filter_output) */
+  int rc = slave->response ? chz_bank_set_responses(c->sh[sc->dev].eng, c->sh[sc->dev].banks[sc->bank].id, sc->idx, 1, (const float *)slave->response) : 0;
+  pthread_mutex_unlock(&slave->response_mutex);
+  pthread_mutex_unlock(&c->lock);
+  if (rc != 0) fprintf(stderr, "set_filter: %s\n", chz_last_error());
+  return rc == 0 ? 0 : -1;
+}
+/* a pooled REAL master that has not run became an engine in place (create_input_impl, force_engine): the slaves registered on it so far
+   become engine slaves, buffers and responses kept.  Called WITHOUT master->filter_mutex (the engine's completion path takes the context's
+   lock first and that mutex second); nothing runs on the master yet. */
+static int rmini_finish_conversion(struct filter_in *master) {
+  if (master->fwd_plan == NULL || is_mini_master(master)) return 0;
+  struct minictx *old = (struct minictx *)MCTX(master)->retired_mini;
+  struct rmshared *rs = old ? __atomic_exchange_n(&old->rs, NULL, __ATOMIC_ACQ_REL) : NULL;
+  if (!rs) return 0;
+  int rc = 0;
+  for (int k = 0; k < rs->nsl; k++) {
+    struct filter_out *o = rs->slv[k];
+    if (!o) continue;
+    rmini_delete_output(o);
+    if (engine_attach_output(o, master, o->olen, o->out_type, true) != 0 || engine_upload_response(o) != 0) rc = -1;
+  }
+  rm_unref(rs);                                                    /* the master's own reference */
+  return rc;
+}
+
 int create_filter_output(struct filter_out *slave, struct filter_in *master, int len, enum filtertype out_type) {
   if (master == NULL || slave == NULL || (out_type != SPECTRUM && len <= 0)) return -1;
   if (slave->master == master && slave->olen == len && slave->out_type == out_type && slave->init)
@@ -809,74 +925,14 @@ int create_filter_output(struct filter_out *slave, struct filter_in *master, int
   set_filter_weights(slave, 1.0, 0.0);
   if (is_mini_master(master)) {
     pthread_mutex_lock(&master->filter_mutex);         /* what an undecided master becomes is settled under its mutex (see execute_filter_input) */
-    int r = is_mini_master(master) ? mini_create_output(slave, master, len, out_type) : 0;
+    int r = !is_mini_master(master) ? 0 : master->in_type == REAL ? rmini_create_output(slave, master, len, out_type) : mini_create_output(slave, master, len, out_type);
     if (r == 2)                            /* a slave no pooled instance serves, on a master still undecided: it becomes a full engine, in place */
       r = create_input_impl(master, master->ilen, master->impulse_length, master->in_type, true);
     pthread_mutex_unlock(&master->filter_mutex);
+    if (r >= 0 && rmini_finish_conversion(master) != 0) r = -1;
     if (r < 0) { slave->init = false; slave->master = NULL; return -1; }
   }
-  if (!is_mini_master(master) && (out_type == COMPLEX || out_type == REAL)) {
-    struct mctx *c = MCTX(master);
-    bool const real = out_type == REAL;
-    slave->bins = real ? slave->points / 2 + 1 : slave->points;    /* src/filter.c:346,374 */
-    slave->fdomain = lmalloc(sizeof(float complex) * (size_t)slave->bins);
-    struct sctx *sc = calloc(1, sizeof *sc);
-    if (sc) sc->kind = CTX_SLAVE;
-    if (real) {
-      slave->output_buffer.r = lmalloc(sizeof(float) * (size_t)slave->points);
-      if (slave->output_buffer.r) { memset(slave->output_buffer.r, 0, sizeof(float) * (size_t)slave->points); slave->output.r = slave->output_buffer.r + slave->points - len; }   /* src/filter.c:385 */
-    } else {
-      slave->output_buffer.c = lmalloc(sizeof(float complex) * (size_t)slave->points);
-      if (slave->output_buffer.c) { memset(slave->output_buffer.c, 0, sizeof(float complex) * (size_t)slave->points); slave->output.c = slave->output_buffer.c + slave->bins - len; }  /* src/filter.c:357 */
-    }
-    if (!slave->fdomain || (!slave->output_buffer.c && !slave->output_buffer.r) || !sc) { FREE(slave->fdomain); FREE(slave->output_buffer.c); FREE(slave->output_buffer.r); free(sc); return -1; }
-    pthread_mutex_lock(&c->lock);
-    stage_wrlock(c);
-    /* which device: the first one that still has room in its share of shard_channels slaves (creation order fills device 0, then 1, ...:
-       contiguous blocks); with every share full, the one with the fewest slaves */
-    int dv = 0;
-    for (int g = 0; g < c->nsh; g++) if (c->sh[g].nslaves < c->shard_channels) { dv = g; goto chosen; }
-    for (int g = 1; g < c->nsh; g++) if (c->sh[g].nslaves < c->sh[dv].nslaves) dv = g;
-  chosen:;
-    struct shard *const sh = &c->sh[dv];
-    int bi = bank_for(c, sh, slave->points, len, real);
-    if (bi < 0) {
-      stage_wrunlock(c);
-      pthread_mutex_unlock(&c->lock);
-      fprintf(stderr, "create_filter_output: no device kernel for P=%d\n", slave->points);
-      FREE(slave->fdomain); FREE(slave->output_buffer.c); FREE(slave->output_buffer.r); free(sc);
-      return -1;
-    }
-    struct hbank *b = &sh->banks[bi];
-    sc->dev = dv; sc->bank = bi; sc->idx = b->n; sc->epoch = 1; sc->n0 = NAN;
-    sc->shard = c->next_shard++ % c->wshards;
-    b->slaves[b->n] = slave; b->shift[b->n] = 0;
-    /* the device row must hold the descriptor of the shift the host believes it holds: a channel that only ever asks for shift 0
-       (the centre channel of a complex front end) would otherwise never send one and read an empty row */
-    if (chz_bank_set_shifts(sh->eng, b->id, b->n, 1, &b->shift[b->n]) != 0) {
-      stage_wrunlock(c);
-      pthread_mutex_unlock(&c->lock);
-      fprintf(stderr, "create_filter_output: %s\n", chz_last_error());
-      FREE(slave->fdomain); FREE(slave->output_buffer.c); FREE(slave->output_buffer.r); free(sc);
-      return -1;
-    }
-    if (!real && master->in_type == COMPLEX) {
-      /* likewise the beam form at this index (a reused index may still hold an earlier occupant's; radio.c sets out.beam BEFORE the demodulator creates
-         the filter output, src/radio.c:938-940, and create_filter_output has just reset the weights, src/filter.c:341) */
-      unsigned char const on = slave->beam ? 1 : 0;
-      if (b->beam_on[b->n] != on || on) {
-        double const ab[4] = {creal(slave->alpha), cimag(slave->alpha), creal(slave->beta), cimag(slave->beta)};
-        b->beam_on[b->n] = on; memcpy(b->beam_ab + 4 * b->n, ab, sizeof ab);
-        chz_bank_set_beam(sh->eng, b->id, b->n, 1, ab, &on);
-      }
-    }
-    for (int s = 0; s < ND; s++) b->stage_epoch[s][b->n] = 0;
-    b->n++; sh->nslaves++;
-    slave->rev_plan = (fftwf_plan)(void *)sc;
-    sync_notches(c, master);               /* radio.c installs the list right after create_filter_input (src/radio.c:601-620): uploaded before block 0, not by it */
-    stage_wrunlock(c);
-    pthread_mutex_unlock(&c->lock);
-  }
+  if (!is_mini_master(master) && (out_type == COMPLEX || out_type == REAL) && engine_attach_output(slave, master, len, out_type, false) != 0) return -1;
   /* SPECTRUM: no buffers, no plan: a block clock only (src/filter.c:368-371) */
 done:;
   slave->next_jobnum = __atomic_load_n(&master->next_jobnum, __ATOMIC_RELAXED);   /* src/filter.c:413 */
@@ -899,6 +955,7 @@ int delete_filter_output(struct filter_out *slave) {
      master, src/filter.c:943-957): what hangs off rev_plan says what it is by itself */
   int const kind = slave->rev_plan ? *(const int *)(const void *)slave->rev_plan : 0;
   if (kind == CTX_MSLAVE) mini_delete_output(slave);
+  else if (kind == CTX_RSLAVE) rmini_delete_output(slave);
   else if (kind == CTX_SLAVE && !(slave->master && slave->master->fwd_plan && !is_mini_master(slave->master))) {
     free(SCTX(slave));                     /* the master went first and took the banks' book-keeping (and the engines) with it */
     slave->rev_plan = NULL;
@@ -1068,7 +1125,7 @@ int execute_filter_input(struct filter_in *const f) {
       if (is_mini_master(f) && !((struct minictx *)(void *)f->fwd_plan)->decided)
         r = create_input_impl(f, f->ilen, f->impulse_length, f->in_type, true);
       pthread_mutex_unlock(&f->filter_mutex);
-      if (r != 0) return -1;
+      if (r != 0 || rmini_finish_conversion(f) != 0) return -1;
     }
     if (is_mini_master(f)) return mini_execute_input(f);
   }
@@ -1484,6 +1541,7 @@ int execute_filter_output(struct filter_out *const slave, int const shift) {
   bool const ready = slave->response != NULL && dst != NULL;
   pthread_mutex_unlock(&slave->response_mutex);
   if (!ready) return 0;                                            /* src/filter.c:715-718 */
+  if (is_rmini_slave(slave)) return is_mini_master(master) ? rmini_execute_output(slave, shift, slot, job) : -1;
   if (is_mini_master(master)) return mini_execute_output(slave, shift, slot);
 
   struct mctx *c = MCTX(master);
@@ -1857,6 +1915,7 @@ int set_filter(struct filter_out *const slave, double low, double high, double c
   __atomic_store_n(&slave->response, response, __ATOMIC_RELEASE);   /* execute_filter_input tests it for NULL without this mutex */
   pthread_mutex_unlock(&slave->response_mutex);
   free(old);
+  if (is_rmini_slave(slave)) return rmini_set_response(slave, response);
   if (slave->rev_plan && is_mini_master(slave->master)) {
     struct msctx *ms = (struct msctx *)(void *)slave->rev_plan;
     if (chz_mini_set_response(ms->pool->h, ms->inst, (const float *)response) != 0) { fprintf(stderr, "set_filter: %s\n", chz_last_error()); return -1; }
@@ -1874,6 +1933,21 @@ int set_filter(struct filter_out *const slave, double low, double high, double c
     if (rc != 0) { fprintf(stderr, "set_filter: %s\n", chz_last_error()); return -1; }
   }
   return 0;
+}
+
+/* include/ka9q_filter_hip_ext.h */
+int ka9q_hip_pool_real_masters(int on) {
+  __atomic_store_n(&Pool_real_masters, on != 0, __ATOMIC_RELAXED);
+  return on != 0 && rmini_available() ? 1 : 0;
+}
+int ka9q_hip_engines_created(void) { return __atomic_load_n(&Engines_created, __ATOMIC_RELAXED); }
+int ka9q_hip_real_master_pools(int *instances) {
+  int pools = 0, used = 0;
+  pthread_mutex_lock(&Mini_registry_lock);
+  for (struct rminipool *p = Rmini_pools; p; p = p->next) { pools++; used += p->used; }
+  pthread_mutex_unlock(&Mini_registry_lock);
+  if (instances) *instances = used;
+  return pools;
 }
 
 /* ------------------------------------------------------------------------- */

@@ -65,6 +65,7 @@ SYMBOLS = [
     "chz_bank_set_demod", "chz_bank_pcm_stride", "chz_bank_set_pcm_stride", "chz_bank_read_pcm", "chz_bank_read_pcm_async",
     "chz_comm_unique_id", "chz_comm_create", "chz_comm_create_file", "chz_comm_destroy", "chz_comm_rank", "chz_comm_world",
     "chz_mini_create", "chz_mini_destroy", "chz_mini_capacity", "chz_mini_add", "chz_mini_release", "chz_mini_set_response", "chz_mini_execute",
+    "chz_rmini_create", "chz_rmini_destroy", "chz_rmini_check", "chz_rmini_capacity", "chz_rmini_add", "chz_rmini_release", "chz_rmini_set_response", "chz_rmini_execute",
     "chz_comm_barrier", "chz_comm_allreduce_max", "chz_spectrum_broadcast", "chz_spectrum_exchange_rows", "chz_run_blocks_sharded",
     "chz_comm_create_local", "chz_spectrum_broadcast_local", "chz_set_option",
     "chz_welch_create", "chz_welch_destroy", "chz_welch_set_window", "chz_welch_configure", "chz_welch_poll", "chz_welch_read", "chz_welch_read_async",
@@ -133,6 +134,14 @@ def lib():
         L.chz_mini_release.argtypes = [_vp, _i]
         L.chz_mini_set_response.argtypes = [_vp, _i, _vp]
         L.chz_mini_execute.argtypes = [_vp, _i, _vp, _vp, _vp, _vp, _vp]
+        L.chz_rmini_create.argtypes = [C.POINTER(_vp), _i, _i, _i, _vp, _vp, _i, _i]
+        L.chz_rmini_destroy.argtypes = [_vp]; L.chz_rmini_destroy.restype = None
+        L.chz_rmini_check.argtypes = [_i, _i, _i, _vp, _vp]
+        L.chz_rmini_capacity.argtypes = [_vp]
+        L.chz_rmini_add.argtypes = [_vp]
+        L.chz_rmini_release.argtypes = [_vp, _i]
+        L.chz_rmini_set_response.argtypes = [_vp, _i, _i, _vp]
+        L.chz_rmini_execute.argtypes = [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]
         L.chz_comm_unique_id.argtypes = [_vp]
         L.chz_comm_create.argtypes = [C.POINTER(_vp), _i, _i, _vp, _i]
         L.chz_comm_create_file.argtypes = [C.POINTER(_vp), _i, _i, C.c_char_p, _i, _d]
@@ -692,6 +701,67 @@ class MiniPool:
     def close(self):
         if self._h:
             lib().chz_mini_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RealMiniPool:
+    """Pool of small REAL inline masters of one geometry with their decimating slaves (wfm, stereod, rdsd, packetd, ctcss).
+
+    slaves: list of (olen, out_type) with out_type 1 = COMPLEX, 2 = REAL."""
+
+    def __init__(self, L, M, slaves, capacity, device=0):
+        self._h = _vp()
+        ol = np.ascontiguousarray([s[0] for s in slaves], np.int32)
+        ot = np.ascontiguousarray([s[1] for s in slaves], np.int32)
+        _check(lib().chz_rmini_create(C.byref(self._h), L, M, len(slaves), ol.ctypes.data, ot.ctypes.data, capacity, device))
+        self.L, self.M, self.N, self.capacity = L, M, L + M - 1, capacity
+        self.slaves = [(int(a), int(b)) for a, b in slaves]
+        self.P = [self.N * a // L for a, _ in self.slaves]
+
+    @staticmethod
+    def check(L, M, slaves):
+        """Would a pool of this geometry be created?  Raises ChzError with the reason if not; touches no device."""
+        ol = np.ascontiguousarray([s[0] for s in slaves], np.int32)
+        ot = np.ascontiguousarray([s[1] for s in slaves], np.int32)
+        _check(lib().chz_rmini_check(L, M, len(slaves), ol.ctypes.data, ot.ctypes.data))
+
+    def add(self):
+        return _check(lib().chz_rmini_add(self._h))
+
+    def release(self, inst):
+        _check(lib().chz_rmini_release(self._h, inst))
+
+    def set_response(self, inst, slave, resp):
+        r = np.ascontiguousarray(resp, np.complex64).reshape(-1)
+        assert r.shape[0] == self.P[slave]
+        _check(lib().chz_rmini_set_response(self._h, inst, slave, r.ctypes.data))
+
+    def execute(self, insts, windows, shifts=None, mask=None, isb=None, out=None):
+        """windows: [n][N] float32 (M-1 old + L new samples each); shifts, isb: [n][nslaves]; mask: [n] bit s = run slave s.
+        Returns one array per slave, [n][olen_s] complex64 or float32; rows of slaves the mask leaves out keep what `out` held."""
+        insts = np.ascontiguousarray(insts, np.int32)
+        n, ns = insts.shape[0], len(self.slaves)
+        win = np.ascontiguousarray(windows, np.float32).reshape(n, self.N)
+        if out is None:
+            out = [np.zeros((n, a), np.complex64 if t == 1 else np.float32) for a, t in self.slaves]
+        wp = (_vp * n)(*[win[i].ctypes.data for i in range(n)])
+        op = (_vp * (n * ns))(*[out[s][i].ctypes.data for i in range(n) for s in range(ns)])
+        sh = np.ascontiguousarray(shifts, np.int32).reshape(n, ns) if shifts is not None else None
+        mk = np.ascontiguousarray(mask, np.uint8).reshape(n) if mask is not None else None
+        fl = np.ascontiguousarray(isb, np.uint8).reshape(n, ns) if isb is not None else None
+        _check(lib().chz_rmini_execute(self._h, n, insts.ctypes.data, wp, sh.ctypes.data if sh is not None else None,
+                                       mk.ctypes.data if mk is not None else None, fl.ctypes.data if fl is not None else None, op))
+        return out
+
+    def close(self):
+        if self._h:
+            lib().chz_rmini_destroy(self._h)
             self._h = _vp()
 
     def __del__(self):

@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.." || exit 1
 python -m pytest tests/test_engine_emulated.py -q -k refuses || exit 1        # builds tests/hipemu/libchz_hip_emu.so
 LIBEMU=$PWD/tests/hipemu/libchz_hip_emu.so
 if [ "$TSAN" = 1 ]; then     # the engine's threading under ThreadSanitizer (tests/c/engine_driver.c, and tests/c/nb_welch_driver.c with spectrum analysers attached; ~6 min each)
-  CHZ_TEST_TSAN_ENGINE=1 python -m pytest tests/test_engine_emulated.py tests/test_welch_narrow_emulated.py -q -k "thread_sanitizer"; exit $?
+  CHZ_TEST_TSAN_ENGINE=1 python -m pytest tests/test_engine_emulated.py tests/test_welch_narrow_emulated.py tests/test_dropin_rmini.py -q -k "thread_sanitizer"; exit $?
 fi
 if [ "$ASAN" = 1 ]; then     # the engine's host code AND the kernels under AddressSanitizer (61 tests clean in round 2; leave the long ones out with -k)
   g++ -std=c++17 -O1 -g -fPIC -shared -fsanitize=address -fno-omit-frame-pointer -DHIPEMU -DHIPEMU_HOST -I tests/hipemu -I ka9q-radio_amd/csrc \
