@@ -3041,6 +3041,11 @@ __global__ void __launch_bounds__(64) demod_linear_tail(DemodParams p) {
   const DemodChan c = p.chan[ch];
   if (!c.on) return;
   DemodState st = p.state[ch];
+  // every lane holds the record before lane 0 may store its successor: demod_fm_wave's hand-off to fm_tone_lanes stores it with no
+  // wave-wide operation in between when the squelch runs on the SNR alone (no amplitude-variance sums).  Lanes in lockstep load
+  // first anyway; where they do not (the fiber emulator runs them in turn) a lane that read the stored record stepped the squelch
+  // sequencer a second time and its part of the block went missing from the hand-off
+  CHZ_WAVE_SYNC();
   float2* xs = reinterpret_cast<float2*>(esh + p.olen);
   if (c.kind == 1) {                                                           // wave-uniform
     if (p.fm_lanes != 0 && c.pll_enable == 0) return;                           // demod_fm_lanes has served this channel

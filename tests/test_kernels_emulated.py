@@ -854,12 +854,20 @@ def test_linear_pll_kernel(emu, monkeypatch, path):
 
 
 def test_pll_one_channel_per_lane_equals_one_lane_per_wavefront(emu, monkeypatch):
+    _pll_lanes_against_lane0(emu, monkeypatch, 240, 0.02)
+
+
+def test_pll_one_channel_per_lane_equals_one_lane_per_wavefront_ragged_tile(emu, monkeypatch):
+    _pll_lanes_against_lane0(emu, monkeypatch, 250, 0.01)      # pll_lanes' last tile holds 10 of 16 samples; 10 ms: 5 samples a slice
+
+
+def _pll_lanes_against_lane0(emu, monkeypatch, N, bt):
     """round 3: the carrier PLLs of a launch run in a pass of their own, one CHANNEL per lane (pll_lanes: 64 channels' blocks
     transposed through LDS tile by tile), instead of one lane of every channel's wavefront walking its block.  Same statements in
     the same order: status records, PLL state and PCM must agree BIT FOR BIT, over 150 channels (three workgroups, the last one
     ragged) of which every third has no PLL and some are FM or switched off."""
     from test_oracle_vs_reference import _coherent_case
-    nblk, N, bt = 12, 240, 0.02
+    nblk = 12
     nch = 150
     kws = [PLL_CASES[i % 4] for i in range(nch)]
     bb0, pw0 = _coherent_case(np.random.default_rng(3), nblk, N, False)
@@ -874,7 +882,7 @@ def test_pll_one_channel_per_lane_equals_one_lane_per_wavefront(emu, monkeypatch
         chan = (_DemodChan * nch)(); state = (_DemodState * nch)(); status = (ol.LinStatus * nch)(); ext = (_DemodExt * nch)()
         emu.emu_demod_ext_init(ext, nch)
         for i, kw in enumerate(kws):
-            p = ol.lin_params(**kw)
+            p = ol.lin_params(samprate=float(round(N / bt)), **kw)
             c = chan[i]
             for f in _CHAN_FIELDS:
                 setattr(c, f, getattr(p, f))
@@ -943,12 +951,20 @@ def test_fm_pll_and_tone_kernel(emu, monkeypatch, path):
 
 
 def test_fm_loops_one_channel_per_lane_equal_one_lane_per_wavefront(emu, monkeypatch):
+    _fm_lanes_against_lane0(emu, monkeypatch, 480, 0.02)
+
+
+def test_fm_loops_one_channel_per_lane_equal_one_lane_per_wavefront_ragged_tiles(emu, monkeypatch):
+    _fm_lanes_against_lane0(emu, monkeypatch, 250, 0.01)       # ragged last tiles in fm_pll_lanes (10 of 16) and fm_tone_lanes (26 of 32)
+
+
+def _fm_lanes_against_lane0(emu, monkeypatch, N, bt):
     """FM's PLL demodulator and PL-tone detector in passes of their own, one channel per lane (fm_front_k, fm_pll_lanes, fm_tone_lanes,
     fm_finish around demod_linear_tail), against the one-kernel path where lane 0 of the channel's wavefront walks the block: the
     same statements, so status records, PCM and the loops' state must come out bit for bit the same -- 70 channels over two lane
     groups, every FM2 case, some switched off, squelch opening and closing on the way."""
     from test_oracle_vs_reference import _fm_case
-    nblk, N, fs, bt = 40, 480, 24000.0, 0.02
+    nblk, fs = 40, float(round(N / bt))
     nch = 70
     cases = [FM2_CASES[i % len(FM2_CASES)] for i in range(nch)]
     sig = [_fm_case(np.random.default_rng(300 + k), nblk, N, fs, tone=FM2_CASES[k][1], last=30) for k in range(len(FM2_CASES))]
@@ -965,7 +981,7 @@ def test_fm_loops_one_channel_per_lane_equal_one_lane_per_wavefront(emu, monkeyp
         chan = (_DemodChan * nch)(); state = (_DemodState * nch)(); status = (ol.LinStatus * nch)(); ext = (_DemodExt * nch)()
         emu.emu_demod_ext_init(ext, nch)
         for i, (kw, _) in enumerate(cases):
-            p = ol.fm_params(**kw)
+            p = ol.fm_params(samprate=fs, **kw)
             c = chan[i]
             for f in _CHAN_FIELDS:
                 setattr(c, f, getattr(p, f))
@@ -985,9 +1001,13 @@ def test_fm_loops_one_channel_per_lane_equal_one_lane_per_wavefront(emu, monkeyp
         assert results[0][b] == results[1][b], b
 
 
-def random_demod_channels(seed=99, nblk=30, N=240, fs=12000.0):
-    """24 channels with randomly drawn demodulator settings (linear and FM alternating) and their test signals."""
+def random_demod_channels(seed=99, nblk=30, N=240, fs=12000.0, blocktime=None):
+    """24 channels with randomly drawn demodulator settings (linear and FM alternating) and their test signals.
+    blocktime=None keeps the historical draw (the linear channels at lin_params' default sample rate, whatever `fs` says: the device
+    sweep and the scale tests import exactly those channels); with a block time every channel runs at fs = N / blocktime."""
     from test_oracle_vs_reference import _demod_case, _fm_case, _coherent_case
+    if blocktime is not None:
+        fs = float(round(N / blocktime))          # (700 / .07 is 10000.000000000002 in binary: radiod's sample rates are integers)
     rng = np.random.default_rng(seed)
     encs = [ol.PCM_S16BE, ol.PCM_S16LE, ol.PCM_F32LE, ol.PCM_F32BE, ol.PCM_MULAW, ol.PCM_ALAW, ol.PCM_F16LE, ol.PCM_F16BE]
     params, oracles, bbs, powers, ests = [], [], [], [], []
@@ -999,6 +1019,8 @@ def random_demod_channels(seed=99, nblk=30, N=240, fs=12000.0):
                       snr_squelch=bool(rng.integers(0, 3) == 0), squelch_tail=int(rng.integers(0, 4)), tuned=bool(rng.integers(0, 8) > 0),
                       headroom_db=float(rng.uniform(-25, -5)), dc_alpha=float(rng.choice([0.0, 0.002])), bandwidth=float(rng.uniform(500, 6000)),
                       gain_db=float(rng.uniform(20, 70)), pll=pll, pll_bw=float(rng.choice([20.0, 50.0])))
+            if blocktime is not None:
+                kw["samprate"] = fs
             p = ol.lin_params(**kw)
             bb, power = (_coherent_case(np.random.default_rng(3), 90, N, False) if pll else _demod_case(np.random.default_rng(2000 + i), nblk, N))
             bb, power = bb[:nblk], power[:nblk].copy()
@@ -1018,19 +1040,9 @@ def random_demod_channels(seed=99, nblk=30, N=240, fs=12000.0):
     return params, oracles, bbs, powers, ests
 
 
-@pytest.mark.parametrize("N", [240, 250])                # 250: the lane kernels' last tile is a partial one (10 of 16 samples)
-@pytest.mark.parametrize("path", ["lanes", "wave"])      # demod_lin_lanes (one channel per lane) / demod_linear_tail (a wavefront per channel)
-def test_demodulator_kernel_random_parameter_sweep(emu, monkeypatch, path, N):
-    if path == "wave":
-        monkeypatch.setenv("EMU_DEMOD_WAVE", "1")
-    else:
-        monkeypatch.delenv("EMU_DEMOD_WAVE", raising=False)
-    """Twenty-four channels with randomly drawn demodulator settings -- linear and FM side by side in ONE launch, every PCM encoding,
-    AGC on and off, envelope / carrier removal, squelch variants, PLLs, tone squelch -- run for 30 blocks on the emulated kernel
-    against the restated demodulators (which the same kind of sweep pins to the reference's own code)."""
+def _run_emulated_against_restatement(emu, params, oracles, bbs, powers, ests, nblk, N, bt):
+    """The emulated demodulator stage (every channel in ONE launch per block) against the restated demodulators, block after block."""
     from test_oracle_vs_reference import _cmp_pcm
-    nblk = 30
-    params, oracles, bbs, powers, ests = random_demod_channels(99, nblk, N, fs=50.0 * N)
     nch = len(params)
     chan = (_DemodChan * nch)(); state = (_DemodState * nch)(); status = (ol.LinStatus * nch)(); ext = (_DemodExt * nch)()
     emu.emu_demod_ext_init(ext, nch)
@@ -1045,15 +1057,77 @@ def test_demodulator_kernel_random_parameter_sweep(emu, monkeypatch, path, N):
             state[i].gain = p.gain; state[i].squelch_open = 1
             state[i].squelch_state = (p.squelch_tail + 4) if not (p.snr_squelch or p.pll_enable) else 0
     pcm = np.zeros((nch, N * 8), np.uint8)
+    frames = set()
     for b in range(nblk):
         x = np.ascontiguousarray(np.stack([bbs[i][b] for i in range(nch)]))
         pw = np.array([powers[i][b] for i in range(nch)]); ne = np.array([ests[i][b] for i in range(nch)])
-        assert emu.emu_demod(x.ctypes.data, pw.ctypes.data, ne.ctypes.data, chan, state, status, pcm.ctypes.data, nch, N, b, 0.02, ext) == 0
+        assert emu.emu_demod(x.ctypes.data, pw.ctypes.data, ne.ctypes.data, chan, state, status, pcm.ctypes.data, nch, N, b, bt, ext) == 0
         for i, p in enumerate(params):
-            want, st = oracles[i].block(bbs[i][b], powers[i][b], ests[i][b], 0.02)
+            want, st = oracles[i].block(bbs[i][b], powers[i][b], ests[i][b], bt)
             got = status[i]
             assert (got.frame, got.mute, got.squelch_state, got.pll_lock, got.tone_mute) == (st.frame, st.mute, st.squelch_state, st.pll_lock, st.tone_mute), (b, i)
             assert got.output_power == pytest.approx(st.output_power, rel=3e-6, abs=1e-300), (b, i)
+            frames.add((i, st.frame, st.squelch_state))
             if st.frame == ol.FRAME_DATA:
                 nb = ol.pcm_bytes(p.encoding, N * p.channels)
                 assert _cmp_pcm(p, pcm[i, :nb], want, 1e-4 if (p.env and p.dc_alpha) else 6e-6), (b, i)
+    return frames
+
+
+# (olen, blocktime) away from 240 / 480 at 20 ms.  What each one reaches in the kernels:
+#   (250, .02)   a ragged last tile of 16 (10 samples) and of 32 (26)
+#   (120, .01)   a ragged tile of 32 only (120 = 7 * 16 + 8 = 3 * 32 + 24); 0.24 s = 24 blocks
+#   (8, .0005)   a block shorter than one tile and shorter than one 2 ms AGC slice (sps = rint(8 * .002 / .0005) = 32 > N: no slice at all)
+#   (24, .05)    N * .002 / blocktime = 0.96 -> rint = 1, and (100, .5) 0.4 -> 0 -> clamped to 1: a block of less than one slice's worth of samples
+#   (1200, .1)   50 slices a block: more than 32 (one per lane of the peak tree); 0.24 / 0.1 is no integer: the tone decision falls in mid-block
+#   (960, .05)   0.24 / 0.05 = 4.8; (700, .07) 0.24 / 0.07 = 3.43, 35 slices, ragged tiles
+#   (480, .04)   0.24 s = 6 blocks: the tone decision falls on a block edge INSIDE the squelch's closing sequence
+#   (4800, .1)   one large block (the wave kernels hold it in 76,800 B of LDS on the device)
+DEMOD_SHAPES = [(250, .02), (120, .01), (8, .0005), (24, .05), (100, .5), (1200, .1), (960, .05), (700, .07), (480, .04), (4800, .1)]
+
+
+@pytest.mark.parametrize("N", [240, 250])                # 250: the lane kernels' last tile is a partial one (10 of 16 samples)
+@pytest.mark.parametrize("path", ["lanes", "wave"])      # demod_lin_lanes (one channel per lane) / demod_linear_tail (a wavefront per channel)
+def test_demodulator_kernel_random_parameter_sweep(emu, monkeypatch, path, N):
+    """Twenty-four channels with randomly drawn demodulator settings -- linear and FM side by side in ONE launch, every PCM encoding,
+    AGC on and off, envelope / carrier removal, squelch variants, PLLs, tone squelch -- run for 30 blocks on the emulated kernel
+    against the restated demodulators (which the same kind of sweep pins to the reference's own code)."""
+    if path == "wave":
+        monkeypatch.setenv("EMU_DEMOD_WAVE", "1")
+    else:
+        monkeypatch.delenv("EMU_DEMOD_WAVE", raising=False)
+    nblk = 30
+    params, oracles, bbs, powers, ests = random_demod_channels(99, nblk, N, fs=50.0 * N)
+    _run_emulated_against_restatement(emu, params, oracles, bbs, powers, ests, nblk, N, 0.02)
+
+
+@pytest.mark.parametrize("N,bt", DEMOD_SHAPES)
+@pytest.mark.parametrize("path", ["lanes", "wave"])
+def test_demodulator_kernel_random_parameter_sweep_at_other_block_shapes(emu, monkeypatch, path, N, bt):
+    """The same sweep at block sizes and block times away from radiod's default (DEMOD_SHAPES), every channel at fs = N / blocktime."""
+    if path == "wave":
+        monkeypatch.setenv("EMU_DEMOD_WAVE", "1")
+    else:
+        monkeypatch.delenv("EMU_DEMOD_WAVE", raising=False)
+    nblk = 30
+    params, oracles, bbs, powers, ests = random_demod_channels(99, nblk, N, blocktime=bt)
+    _run_emulated_against_restatement(emu, params, oracles, bbs, powers, ests, nblk, N, bt)
+
+
+@pytest.mark.parametrize("N,bt", [(480, .04), (480, .03), (240, .04), (960, .04), (1200, .05), (480, .02), (250, .02)])
+@pytest.mark.parametrize("extend", [False, True])
+@pytest.mark.parametrize("path", ["lanes", "wave"])
+def test_fm_tone_channel_through_the_closing_squelch(emu, monkeypatch, path, extend, N, bt):
+    """One FM channel with a PL tone whose carrier fades at block 26: the squelch's closing sequence (states smax-1 .. 5 still send
+    DATA frames) at block times where the tone detector's 0.24 s window ends inside that sequence."""
+    if path == "wave":
+        monkeypatch.setenv("EMU_DEMOD_WAVE", "1")
+    else:
+        monkeypatch.delenv("EMU_DEMOD_WAVE", raising=False)
+    nblk, fs = 30, float(round(N / bt))
+    p = ol.fm_params(encoding=ol.PCM_F32LE, snr_squelch=True, squelch_tail=2, samprate=fs, bandwidth=8000, threshold_extend=extend, deemph_tc=0, tone_freq=100.0)
+    from test_oracle_vs_reference import _fm_case
+    bb, power = _fm_case(np.random.default_rng(3021), nblk, N, fs, tone=100.0, last=26)
+    frames = _run_emulated_against_restatement(emu, [p], [ol.FmDemod(p)], [bb], [power], [np.full(nblk, 2 * 2e-3 ** 2 / fs)], nblk, N, bt)
+    if bt > .02:      # (at 20 ms the first 0.24 s window has not seen the tone for its whole length: the channel stays muted, the two shapes ride along)
+        assert (0, ol.FRAME_DATA, 7) in frames and (0, ol.FRAME_DATA, 5) in frames and (0, ol.FRAME_SILENCE, 4) in frames

@@ -466,20 +466,34 @@ def _coherent_case(r, nblk, N, square, last=50, first=4):
     return bb, power
 
 
-@pytest.mark.skipif(not ol.have_ref_linear(), reason="oracle/_ref/libka9q_ref_linear.so not built (needs /root/reference)")
-@pytest.mark.parametrize("kw", [
+PLL_KW = [
     dict(pll=True),                                                  # coherent AM: carrier tracking, I channel out
     dict(pll=True, square=True, pll_bw=20.0, channels=2, encoding=ol.PCM_F32LE),  # squaring loop on a BPSK-like signal, I/Q out
     dict(pll=True, env=True, dc_alpha=0.002, pll_bw=50.0, squelch_tail=0, encoding=ol.PCM_S16LE),
-])
+]
+
+
+@pytest.mark.skipif(not ol.have_ref_linear(), reason="oracle/_ref/libka9q_ref_linear.so not built (needs /root/reference)")
+@pytest.mark.parametrize("kw", PLL_KW)
 def test_linear_pll_matches_reference_linear_c(oracle_built, kw):
+    _linear_pll_against_reference(kw, 240, 0.02)
+
+
+@pytest.mark.skipif(not ol.have_ref_linear(), reason="oracle/_ref/libka9q_ref_linear.so not built (needs /root/reference)")
+@pytest.mark.parametrize("kw", PLL_KW)
+@pytest.mark.parametrize("N,bt", [(250, .02), (120, .01), (1200, .1)])    # 12.5 k / 12 k / 12 kHz; 1.8 s of signal each
+def test_linear_pll_matches_reference_linear_c_at_other_block_shapes(oracle_built, kw, N, bt):
+    _linear_pll_against_reference(kw, N, bt)
+
+
+def _linear_pll_against_reference(kw, N, bt):
     # the PLL branch of demod_linear() (src/linear.c:83-153) incl. the lock detector and the squelch it drives, the loop
     # itself from the reference's osc.c
     r = np.random.default_rng(3)             # (on some noise the wide loop runs off to a false lock near fs/4 before the carrier comes up)
-    nblk, N, bt = 90, 240, 0.02
-    bb, power = _coherent_case(r, nblk, N, kw.get("square", False))
-    n0_est = np.full(nblk, 2 * 4e-4 ** 2 / 12000.0)
-    p = ol.lin_params(**kw)
+    nblk, fs = int(round(1.8 / bt)), float(round(N / bt))
+    bb, power = _coherent_case(r, nblk, N, kw.get("square", False), last=int(round(1.0 / bt)), first=int(round(0.08 / bt)))
+    n0_est = np.full(nblk, 2 * 4e-4 ** 2 / fs)
+    p = ol.lin_params(samprate=fs, **kw)
     n0s = np.zeros(nblk); s = np.nan
     for b in range(nblk):
         s = n0_est[b] if np.isnan(s) else s + 0.10 * (n0_est[b] - s)
@@ -510,10 +524,10 @@ def test_linear_pll_matches_reference_linear_c(oracle_built, kw):
                 dt = ">f4" if p.encoding == ol.PCM_F32BE else "<f4"
                 a, w = pcm.view(dt).astype(np.float64), pcm_r[b].view(dt).astype(np.float64)
                 assert np.abs(a - w).max() <= 2e-6 * max(np.abs(w).max(), 1e-30)
-    assert 10 < locked < nblk - 10                                   # it locked on the carrier and let go after it went away
+    assert 0.2 < locked * bt < nblk * bt - 0.2                       # it locked on the carrier and let go after it went away
     assert (ol.FRAME_DATA, 0) in seen and (ol.FRAME_SILENCE, 1) in seen
-    # the loop really tracked the 30 Hz offset while locked
-    assert any(abs(pll_r[b, 4] - 30.0) < 1.0 for b in range(30, 48)) or kw.get("square")
+    # the loop really tracked the offset while locked (30 Hz at 12 kHz: the test signal is laid out in cycles per sample)
+    assert any(abs(pll_r[b, 4] - 30.0 * fs / 12000.0) < 1.0 for b in range(int(0.6 / bt), int(0.96 / bt))) or kw.get("square")
 
 
 def _fm_case(r, nblk, N, fs, tone=0.0, last=26):
@@ -570,20 +584,35 @@ def test_fm_demodulator_matches_reference_fm_c(oracle_built, kw):
     assert (ol.FRAME_DATA, 0) in seen and (ol.FRAME_SILENCE, 0) in seen and (ol.FRAME_SILENCE, 1) in seen
 
 
-@pytest.mark.skipif(not ol.have_ref_fm(), reason="oracle/_ref/libka9q_ref_fm.so not built (needs /root/reference)")
-@pytest.mark.parametrize("kw,tone_sent", [
+FM2_KW = [
     (dict(pll=True, encoding=ol.PCM_F32LE), 0.0),                     # PLL demodulator (src/fm.c:176-203)
     (dict(pll=True, threshold_extend=True), 0.0),
     (dict(tone_freq=100.0), 100.0),                                   # PL tone squelch: the tone is there -> opens after 0.24 s
     (dict(tone_freq=100.0, deemph_tc=0, encoding=ol.PCM_S16LE), 0.0), # ... and is not: stays muted
     (dict(tone_freq=123.0, pll=True), 100.0),                         # the wrong tone
-])
+]
+
+
+@pytest.mark.skipif(not ol.have_ref_fm(), reason="oracle/_ref/libka9q_ref_fm.so not built (needs /root/reference)")
+@pytest.mark.parametrize("kw,tone_sent", FM2_KW)
 def test_fm_pll_and_tone_squelch_match_reference_fm_c(oracle_built, kw, tone_sent):
+    _fm_pll_and_tone_against_reference(kw, tone_sent, 480, 0.02)
+
+
+# 0.24 s of tone integration = 4.8 blocks / 3.43 blocks (the decision falls in mid-block) / 12 blocks of a size that is no multiple of 16
+@pytest.mark.skipif(not ol.have_ref_fm(), reason="oracle/_ref/libka9q_ref_fm.so not built (needs /root/reference)")
+@pytest.mark.parametrize("kw,tone_sent", FM2_KW)
+@pytest.mark.parametrize("N,bt", [(1200, .05), (700, .07), (250, .02)])
+def test_fm_pll_and_tone_squelch_match_reference_fm_c_at_other_block_shapes(oracle_built, kw, tone_sent, N, bt):
+    _fm_pll_and_tone_against_reference(kw, tone_sent, N, bt)
+
+
+def _fm_pll_and_tone_against_reference(kw, tone_sent, N, bt):
     r = np.random.default_rng(len(kw) + 60 + int(tone_sent))
-    nblk, N, fs, bt = 72, 480, 24000.0, 0.02
-    bb, power = _fm_case(r, nblk, N, fs, tone=tone_sent, last=60)    # the tone detector integrates 12 blocks at a time
+    nblk, fs = int(round(1.44 / bt)), float(round(N / bt))
+    bb, power = _fm_case(r, nblk, N, fs, tone=tone_sent, last=int(round(1.2 / bt)))    # the tone detector integrates 0.24 s at a time
     bb = bb.copy(); power = power.copy()
-    p = ol.fm_params(**kw)
+    p = ol.fm_params(samprate=fs, **kw)
     n0_est = (2 * 2e-3 ** 2 / fs) * (1 + 0.1 * r.standard_normal(nblk))
     n0s = np.zeros(nblk); s = np.nan
     for b in range(nblk):
@@ -633,9 +662,26 @@ def _cmp_pcm(p, got, want, tol_f):
     return np.abs(a - w).max() <= tol_f * max(np.abs(w).max(), 1e-30)
 
 
+# (N, blocktime) away from radiod's default 20 ms, which the sweeps have always run (240, 160 and 480 samples a block):
+# 250 (no multiple of 16), 700 (none of 16 or 32), blocks of less than one 2 ms AGC slice (24 * .002 / .05 = 0.96,
+# 100 * .002 / .5 = 0.4, and 8 samples in 0.5 ms where a slice is 32), more than 32 slices a block (0.1 s: 50), block times that do
+# not divide the tone detector's 0.24 s (0.05, 0.07, 0.1), and one large block (4800)
+SHAPES_OTHER = [(250, .02), (120, .01), (8, .0005), (24, .05), (100, .5), (1200, .1), (960, .05), (700, .07), (480, .04), (4800, .1)]
+
+
 @pytest.mark.skipif(not ol.have_ref_linear(), reason="oracle/_ref/libka9q_ref_linear.so not built (needs /root/reference)")
 def test_linear_demodulator_random_parameter_sweep(oracle_built):
-    rng = np.random.default_rng(20260926)
+    _linear_sweep_against_reference(20260926, None)
+
+
+@pytest.mark.skipif(not ol.have_ref_linear(), reason="oracle/_ref/libka9q_ref_linear.so not built (needs /root/reference)")
+def test_linear_demodulator_random_parameter_sweep_at_other_block_shapes(oracle_built):
+    _linear_sweep_against_reference(20261019, SHAPES_OTHER)
+
+
+def _linear_sweep_against_reference(seed, shapes):
+    """shapes None: the draw this sweep has always made (20 ms blocks of 240, 160 or 480 samples); else every shape in turn"""
+    rng = np.random.default_rng(seed)
     encs = [ol.PCM_S16BE, ol.PCM_S16LE, ol.PCM_F32LE, ol.PCM_F32BE, ol.PCM_MULAW, ol.PCM_ALAW]
     for case in range(30):
         kw = dict(channels=int(rng.integers(1, 3)), env=bool(rng.integers(0, 2)), agc=bool(rng.integers(0, 4) > 0),
@@ -644,8 +690,9 @@ def test_linear_demodulator_random_parameter_sweep(oracle_built):
                   recovery_db_per_s=float(rng.uniform(5, 40)), hangtime=float(rng.uniform(0.0, 0.3)),
                   dc_alpha=float(rng.choice([0.0, 0.002, 0.02])), bandwidth=float(rng.uniform(500, 6000)),
                   shift=float(rng.choice([0.0, 0.0, 700.0, -431.5])), gain_db=float(rng.uniform(20, 70)))
-        nblk, N = 24, int(rng.choice([240, 160, 480]))
-        kw["samprate"] = N * 50.0
+        nblk = 24
+        N, bt = (int(rng.choice([240, 160, 480])), 0.02) if shapes is None else shapes[case % len(shapes)]
+        kw["samprate"] = float(round(N / bt))      # (700 / .07 is 10000.000000000002 in binary: radiod's sample rates are integers)
         bb, power = _demod_case(np.random.default_rng(1000 + case), nblk, N, bursts=bool(rng.integers(0, 2))) if nblk >= 16 else (None, None)
         if kw["snr_squelch"]:
             power = power.copy(); power[10:15] = 1e-12
@@ -655,10 +702,10 @@ def test_linear_demodulator_random_parameter_sweep(oracle_built):
         for b in range(nblk):
             s = n0_est[b] if np.isnan(s) else s + 0.10 * (n0_est[b] - s)
             n0s[b] = s
-        pcm_r, frame_r, mute_r, pow_r, gain_r = ol.ref_linear_run(p, bb, power, n0s, 0.02)
+        pcm_r, frame_r, mute_r, pow_r, gain_r = ol.ref_linear_run(p, bb, power, n0s, bt)
         d = ol.LinDemod(p)
         for b in range(nblk):
-            pcm, st = d.block(bb[b], power[b], n0_est[b], 0.02)
+            pcm, st = d.block(bb[b], power[b], n0_est[b], bt)
             assert st.frame == frame_r[b] and st.mute == mute_r[b], (case, kw, b)
             assert st.gain == pytest.approx(gain_r[b], rel=1e-9), (case, b)
             assert st.output_power == pytest.approx(pow_r[b], rel=3e-7, abs=1e-300), (case, b)
@@ -670,7 +717,16 @@ def test_linear_demodulator_random_parameter_sweep(oracle_built):
 
 @pytest.mark.skipif(not ol.have_ref_fm(), reason="oracle/_ref/libka9q_ref_fm.so not built (needs /root/reference)")
 def test_fm_demodulator_random_parameter_sweep(oracle_built):
-    rng = np.random.default_rng(7)
+    _fm_sweep_against_reference(7, [(480, .02)])
+
+
+@pytest.mark.skipif(not ol.have_ref_fm(), reason="oracle/_ref/libka9q_ref_fm.so not built (needs /root/reference)")
+def test_fm_demodulator_random_parameter_sweep_at_other_block_shapes(oracle_built):
+    _fm_sweep_against_reference(8, SHAPES_OTHER)
+
+
+def _fm_sweep_against_reference(seed, shapes):
+    rng = np.random.default_rng(seed)
     encs = [ol.PCM_S16BE, ol.PCM_S16LE, ol.PCM_F32LE, ol.PCM_F32BE, ol.PCM_MULAW, ol.PCM_ALAW]
     for case in range(20):
         tone = float(rng.choice([0.0, 0.0, 100.0, 88.5]))
@@ -679,7 +735,10 @@ def test_fm_demodulator_random_parameter_sweep(oracle_built):
                   headroom_db=float(rng.uniform(-20, -6)), pll=bool(rng.integers(0, 4) == 0), tone_freq=tone,
                   squelch_open=float(rng.uniform(3.0, 8.0)))
         kw["squelch_close"] = kw["squelch_open"] * float(rng.uniform(0.5, 0.9))
-        nblk, N, fs = 52, 480, 24000.0
+        nblk = 52
+        N, bt = shapes[case % len(shapes)]
+        fs = float(round(N / bt))
+        kw["samprate"] = fs
         sent = tone if rng.integers(0, 3) else 0.0
         bb, power = _fm_case(np.random.default_rng(500 + case), nblk, N, fs, tone=sent, last=44)
         p = ol.fm_params(**kw)
@@ -688,10 +747,10 @@ def test_fm_demodulator_random_parameter_sweep(oracle_built):
         for b in range(nblk):
             s = n0_est[b] if np.isnan(s) else s + 0.10 * (n0_est[b] - s)
             n0s[b] = s
-        ref = ol.ref_fm_run(p, bb, power, n0s, 0.02)
+        ref = ol.ref_fm_run(p, bb, power, n0s, bt)
         d = ol.FmDemod(p)
         for b in range(nblk):
-            pcm, st = d.block(bb[b], power[b], n0_est[b], 0.02)
+            pcm, st = d.block(bb[b], power[b], n0_est[b], bt)
             assert st.frame == ref["frame"][b] and st.mute == ref["mute"][b], (case, kw, b)
             assert st.snr == pytest.approx(ref["snr"][b], rel=1e-6, abs=1e-12)
             assert st.tone_deviation == pytest.approx(ref["tonedev"][b], rel=1e-5, abs=1e-6)
