@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+import pcm_edge_cases as pe
 
 pytestmark = pytest.mark.skipif(not ol.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
 
@@ -411,26 +412,48 @@ def test_linear_demodulator_matches_reference_linear_c(oracle_built, kw):
         assert (ol.FRAME_SILENCE, 0) in seen and (ol.FRAME_SILENCE, 1) in seen and (ol.FRAME_DATA, 0) in seen
 
 
+def _reference_at_unit_gain(values, enc):
+    """The reference's own packer fed `values` bit for bit: its demod_linear() at unit gain without AGC (real part out: the I channel)
+    in front of its send_output(); the bytes of the values, the padding of the last block cut off."""
+    N = 240
+    bb = pe.rows(values, 1, N)
+    pcm_r, frame_r, _, _, gain_r = ol.ref_linear_run(pe.unit_gain_params(ol, 1, enc), bb, np.ones(len(bb)), np.full(len(bb), 1e-12), 0.02)
+    assert (frame_r == ol.FRAME_DATA).all() and (gain_r == 1.0).all()
+    return pcm_r.reshape(-1)[:ol.pcm_bytes(enc, len(values))]
+
+
 @pytest.mark.skipif(not ol.have_ref_linear(), reason="oracle/_ref/libka9q_ref_linear.so not built (needs /root/reference)")
 def test_g711_companding_matches_reference_rtp_c(oracle_built):
     # float_to_mulaw / float_to_alaw of the reference's own rtp.c (through export_mulaw / export_alaw in the linear wrapper's
-    # send_output) against the restatement, for every 16-bit level and beyond the clip points: bit-exact
+    # send_output) against the restatement, for every 16-bit level, every tie between two levels with the floats on either side of
+    # it, and beyond the clip points (tests/pcm_edge_cases.py: the values the device's packers are handed): bit-exact
     import ctypes as C
     O = ol.oracle()
     O.chzo_float_to_mulaw.argtypes = [C.c_float]; O.chzo_float_to_mulaw.restype = C.c_ubyte
     O.chzo_float_to_alaw.argtypes = [C.c_float]; O.chzo_float_to_alaw.restype = C.c_ubyte
-    lv = np.concatenate([np.arange(-32768, 32769) / 32768.0, [1.5, -1.5, 3e-5, -3e-5, 0.999999, -0.999999]]).astype(np.float32)
-    N = 240
-    lv = np.concatenate([lv, np.zeros((-len(lv)) % N, np.float32)])
-    bb = (lv + 0j).astype(np.complex64).reshape(-1, N)              # real part out at unit gain: I channel, no AGC
+    lv = np.concatenate([pe.I16_VALUES, np.array([3e-5, -3e-5, 0.999999, -0.999999], np.float32)])
     for enc, fn in ((ol.PCM_MULAW, O.chzo_float_to_mulaw), (ol.PCM_ALAW, O.chzo_float_to_alaw)):
-        p = ol.lin_params(agc=False, gain_db=0.0, encoding=enc)
-        pcm_r, frame_r, _, _, _ = ol.ref_linear_run(p, bb, np.ones(len(bb)), np.full(len(bb), 1e-12), 0.02)
-        assert (frame_r == ol.FRAME_DATA).all()
-        want = pcm_r.reshape(-1)[:len(lv)]
-        got = np.array([fn(float(v)) for v in lv], np.uint8)
-        assert np.array_equal(got, want)
+        want = _reference_at_unit_gain(lv, enc)
+        got = pe.pack(ol, enc, lv)
+        assert np.array_equal(got, want), (enc, lv[got != want][:5], got[got != want][:5], want[got != want][:5])
+        one = np.array([fn(float(v)) for v in lv], np.uint8)                 # the single-sample entry points
+        assert np.array_equal(one, want)
     assert O.chzo_float_to_mulaw(0.0) == 0xFF and O.chzo_float_to_alaw(0.0) == 0x55       # the idle codes
+
+
+@pytest.mark.skipif(not ol.have_ref_linear(), reason="oracle/_ref/libka9q_ref_linear.so not built (needs /root/reference)")
+def test_s16_packing_matches_reference_import_h(oracle_built):
+    # export_s16_le / export_s16_be of the reference's own import.h (src/import.h:90-94: ldexpf, clamp at +-32767, lrintf) by the same
+    # route, at the same values: ties go to the even level, +-1.0 and everything beyond pack as +-32767, never -32768
+    for enc in (ol.PCM_S16LE, ol.PCM_S16BE):
+        want = _reference_at_unit_gain(pe.I16_VALUES, enc)
+        got = pe.pack(ol, enc, pe.I16_VALUES)
+        assert np.array_equal(got, want), (enc, np.flatnonzero(got != want)[:5])
+        v = got.view(">i2" if enc == ol.PCM_S16BE else "<i2").astype(np.int32)
+        x = pe.I16_VALUES.astype(np.float64) * 32768
+        assert v.min() == -32767 and v.max() == 32767
+        inside = np.abs(x) <= 32767
+        assert np.array_equal(v[inside], np.rint(x[inside]).astype(np.int32))            # np.rint: to nearest, ties to even
 
 
 def test_pll_oscillator_matches_reference_osc_c(oracle_built):
@@ -582,6 +605,33 @@ def test_fm_demodulator_matches_reference_fm_c(oracle_built, kw):
                 a, w = pcm.view(dt).astype(np.float64), ref["pcm"][b].view(dt).astype(np.float64)
                 assert np.abs(a - w).max() <= 2e-6 * max(np.abs(w).max(), 1e-30)
     assert (ol.FRAME_DATA, 0) in seen and (ol.FRAME_SILENCE, 0) in seen and (ol.FRAME_SILENCE, 1) in seen
+
+
+@pytest.mark.skipif(not ol.have_ref_fm(), reason="oracle/_ref/libka9q_ref_fm.so not built (needs /root/reference)")
+@pytest.mark.parametrize("encoding", [ol.PCM_S16LE, ol.PCM_S16BE, ol.PCM_MULAW, ol.PCM_ALAW], ids=["s16le", "s16be", "mulaw", "alaw"])
+@pytest.mark.parametrize("kw", pe.FM_CLIP_KW, ids=["deemph+6dB", "flat0dB"])
+def test_fm_demodulator_matches_reference_fm_c_at_the_clip(oracle_built, kw, encoding):
+    # demod_fm() with its audio driven beyond full scale (tests/pcm_edge_cases.py: fm_clip_case): the restatement's frames against the
+    # reference's, exact for S16 and G.711 (_cmp_pcm); about half of the samples sit at the packer's clip.  (The wrapper packs no
+    # binary16, which the reference's gcc build lacks: test_f16_packing_equals_the_references_import_h pins that packer.)
+    bb, power, n0_est = pe.fm_clip_case(7)
+    p = ol.fm_params(encoding=encoding, **kw)
+    n0s = np.zeros(len(bb)); s = np.nan
+    for b in range(len(bb)):
+        s = n0_est[b] if np.isnan(s) else s + 0.10 * (n0_est[b] - s)
+        n0s[b] = s
+    ref = ol.ref_fm_run(p, bb, power, n0s, pe.FM_CLIP_BT)
+    d = ol.FmDemod(p)
+    clipped = []
+    for b in range(len(bb)):
+        pcm, st = d.block(bb[b], power[b], n0_est[b], pe.FM_CLIP_BT)
+        assert st.frame == ref["frame"][b] and st.mute == ref["mute"][b], b
+        if st.frame == ol.FRAME_DATA:
+            assert st.output_power == pytest.approx(ref["power"][b], rel=1e-6)
+            assert _cmp_pcm(p, pcm, ref["pcm"][b][:pcm.size], 2e-6), b
+            clipped.append(pe.clipped_fraction(ol, encoding, ref["pcm"][b][:pcm.size]))
+    assert len(clipped) >= 8
+    assert 0.1 < np.mean(clipped) < 0.9, clipped
 
 
 FM2_KW = [
@@ -769,14 +819,15 @@ def test_f16_packing_equals_the_references_import_h():
         pytest.skip("oracle/_ref/libka9q_ref_f16.so absent (no clang with _Float16)")
     rng = np.random.default_rng(16)
     halfs = np.arange(0x7c00, dtype=np.uint16).view(np.float16).astype(np.float32)          # every finite non-negative binary16
-    mids = (halfs[:-1].astype(np.float64) + halfs[1:].astype(np.float64)) / 2                  # exact ties between neighbours
-    ties = np.concatenate([mids.astype(np.float32), np.nextafter(mids.astype(np.float32), np.float32(0)), np.nextafter(mids.astype(np.float32), np.float32(1e9))])
     rnd = rng.integers(0, 2 ** 32, 4_000_000, dtype=np.uint64).astype(np.uint32).view(np.float32)
     rnd = rnd[np.isfinite(rnd)]
     audio = (rng.standard_normal(1_000_000) * 0.2).astype(np.float32)
     special = np.array([0.0, -0.0, 65504.0, 65519.99, 65520.0, 70000.0, -70000.0, np.inf, -np.inf, 2.0 ** -24, 2.0 ** -25, 2.0 ** -25 * 1.0000001, 2.0 ** -26,
                         6.1035156e-05, 6.0975552e-05, 1e-8, -1e-8], np.float32)
-    x = np.concatenate([halfs, -halfs, ties, -ties, rnd, audio, special])
+    # pe.F16_VALUES: +-halfs, every tie between neighbours with the float32 on either side, the thresholds -- the values the device's
+    # packers are handed (tests/test_gpu_pcm_edges.py)
+    x = np.concatenate([pe.F16_VALUES, rnd, audio, special])
+    assert np.isin(np.concatenate([halfs, -halfs]).view(np.uint32), pe.F16_VALUES.view(np.uint32)).all()
     for be in (0, 1):
         want = np.zeros(x.size, np.uint16)
         ref.ref_export_f16(want.ctypes.data, x.ctypes.data, x.size, be)
