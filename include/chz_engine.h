@@ -413,6 +413,55 @@ int chz_rmini_set_response(chz_rmini *m, int inst, int slave, const float *resp)
 int chz_rmini_execute(chz_rmini *m, int n, const int *inst, const float *const *win, const int *shift, const unsigned char *mask,
                       const unsigned char *isb, float *const *out);
 
+/* ---- Pooled stereo broadcast-FM decoders: demod_wfm() (src/wfm.c:134-281) from a 384 kHz channel's baseband to its 48 kHz PCM ------
+ * One launch serves every instance that is due, one workgroup per request: squelch, discriminator, statistics, the composite filter
+ * (a REAL master of L = 384 kHz x blocktime samples, M = L + 1, with its mono, pilot and L-R slaves -- chz_rmini_*'s transform and
+ * gather rules), pilot detector, stereo matrix, de-emphasis and PCM packing.  The decoder is a recurrence over blocks: phase_memory,
+ * the squelch sequencer, foffset / pdeviation, the de-emphasis states and the composite filter's history live on the device, per
+ * instance, all zero after chz_wfm_add.  Limits, refused at chz_wfm_create / chz_wfm_check and nowhere else: what chz_rmini_create
+ * refuses for that master, and a 19 or 38 kHz bin shift that is no multiple of 4 or leaves a remainder (src/wfm.c:96,101) -- 10 ms
+ * and 20 ms blocks remain.
+ * Option wfm_deemph_lanes (chz_set_option, read by chz_wfm_create): how many lanes share a block's de-emphasis recurrence, 64 (default)
+ * = runs of consecutive samples reduced to affine maps and replayed, 1 = one lane walks the block (a measurement switch). */
+typedef struct chz_wfm chz_wfm;
+typedef struct chz_wfm_params {
+  int stereo_enable;    /* chan->fm.stereo_enable: look for the pilot */
+  int encoding;         /* CHZ_PCM_* */
+  int squelch_tail;     /* chan->squelch.tail, blocks */
+  double squelch_open, squelch_close;   /* power ratios */
+  double bandwidth;     /* |max_IF - min_IF|, Hz */
+  double headroom;      /* amplitude ratio */
+  double deemph_rate, deemph_gain;      /* chan->fm.rate (0: no de-emphasis), chan->fm.gain */
+} chz_wfm_params;
+typedef struct chz_wfm_status {
+  int frame;            /* 0: PCM present; 1: no samples (squelch closed: mute, pcm untouched) */
+  int mute, squelch_state;
+  int channels;         /* 2 with the pilot present, else 1: pcm holds olen * channels samples */
+  int pilot_present;
+  double snr;           /* chan->fm.snr */
+  double foffset, pdeviation, output_power;
+  double gain;          /* chan->output.gain = 2 headroom 384000 / bandwidth */
+  double subc_amp;      /* mean |pilot|^2 (chan->tp1); 0 where the pilot filter did not run */
+} chz_wfm_status;
+int chz_wfm_check(double blocktime);                                            /* would chz_wfm_create take this block time? 0, or < 0 and chz_last_error(); touches no device */
+int chz_wfm_create(chz_wfm **out, double blocktime, int capacity, int device);
+void chz_wfm_destroy(chz_wfm *m);
+int chz_wfm_capacity(const chz_wfm *m);
+int chz_wfm_geometry(const chz_wfm *m, int out6[6]);                            /* L, N, olen, P, pilot_shift, subc_shift */
+int chz_wfm_add(chz_wfm *m);                                                    /* -> instance index */
+int chz_wfm_release(chz_wfm *m, int inst);
+int chz_wfm_set_params(chz_wfm *m, int inst, const chz_wfm_params *p);
+int chz_wfm_set_response(chz_wfm *m, int inst, int slave, const float *resp);   /* slave 0 mono, 1 pilot, 2 L-R; P complex, as chz_rmini_set_response */
+/* One block of n decoders, one H2D, ONE launch and one D2H per chunk of `capacity`: instance inst[i] (at most once in a call) takes the
+ * L complex samples at bb[i] -- host memory (bb_on_device = 0), or device memory that is complete before the call (1: e.g. a row of
+ * chz_bank_output_device() after chz_slot_sync; read in place) --, the channel's bb_power[i] (chz_bank_read_power) and the host's
+ * smoothed noise density n0[i]; pcm[i] receives olen * status[i].channels samples of the instance's encoding and stays untouched when
+ * status[i].frame = 1.  What comes back per request is its status record and one PCM row as large as the instance can fill (olen samples,
+ * twice as many with stereo_enable).  Every request is checked before the first launch: a refused call has written nothing and advanced no state.
+ * Synchronous, thread-safe. */
+int chz_wfm_execute(chz_wfm *m, int n, const int *inst, const float *const *bb, int bb_on_device, const double *bb_power, const double *n0,
+                    void *const *pcm, chz_wfm_status *status);
+
 /* ---- Welch power spectra of the raw input: radiod's wideband spectrum analyser (wideband_poll(), src/spectrum.c:308-522) on the
  * samples the engine's input ring holds (float REAL, float COMPLEX or the int16 of chz_input_write_i16).  A bank holds `capacity`
  * analysers sharing one fft_n (= lrint(samprate / rbw): any length from 8 to 2^20 points; one with a prime factor above 13 runs as

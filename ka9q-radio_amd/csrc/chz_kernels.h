@@ -3446,6 +3446,68 @@ struct RminiParams {
   RminiSlave s[CHZ_RMINI_MAX_SLAVES];
 };
 
+// the Hermitian split behind the packed forward transform: Z (A or B) -> the master's H + 1 bins in S = lds[0, H]
+__device__ __forceinline__ void rmini_split(const float2* Z, float2* S, const float2* __restrict__ tw_split, int H, int tid, int nthr) {
+  for (int k = tid; 2 * k <= H; k += nthr) {                               // X_k = (Z_k + conj Z_{H-k})/2 - i/2 W^k (Z_k - conj Z_{H-k})
+    const int kk = H - k;
+    const float2 zk = Z[k], zm = Z[k == 0 ? 0 : kk];
+    const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
+    const float2 o = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
+    const float2 t = cmul(o, tw_split[k]);
+    const float2 u = cmul(make_float2(o.x, -o.y), tw_split[kk]);           // bin H - k: conj(e), conj(o)
+    S[k] = make_float2(e.x + t.x, e.y + t.y);
+    if (kk != k) S[kk] = make_float2(e.x + u.x, u.y - e.y);
+  }
+  __syncthreads();
+}
+// one slave of a REAL master whose m_bins bins sit in S: gather x response into Y, backward transform between Y and Y + P; returns
+// where the P samples are (the last olen of them leave).  The caller puts a barrier behind its reads before the next slave runs.
+__device__ __forceinline__ const float2* rmini_slave(const float2* S, float2* Y, const RminiSlave& sl, const ChanDesc d, const int& isb, int m_bins,
+                                                     int tid, int nthr) {
+  const MiniParams& sm = sl.m;
+  const int P = sm.N;
+  const float2* __restrict__ Hr = sm.resp + (size_t)d.row * P;
+  float2* W = Y + P;
+  if (!sl.real_out) {
+    for (int i = tid; i < P; i += nthr) {
+      int t = i - (P + 1) / 2; if (t < 0) t += P;                          // rank from the most negative bin
+      const int u = t - d.t0;
+      const bool ok = (u >= 0) && (u < d.cnt);
+      const int src = d.src0 + d.dir * u;
+      float2 v = make_float2(0.f, 0.f);
+      if (ok) { v = S[src]; if (d.conj) v.y = -v.y; v = cmul(v, Hr[i]); }
+      Y[i] = v;
+    }
+    __syncthreads();
+    if (isb) {                                                             // src/filter.c:895-909: pairs p = 1 .. s_bins/2 - 1 (an odd P leaves its innermost pair alone)
+      for (int q = tid; q < P / 2; q += nthr) {
+        if (q == 0) { Y[0] = make_float2(0.f, 0.f); continue; }
+        const float2 pos = Y[q], neg = Y[P - q];
+        Y[q] = make_float2(pos.x + neg.x, pos.y - neg.y);                  // pos + conj(neg)
+        Y[P - q] = make_float2(neg.x - pos.x, neg.y + pos.y);              // neg - conj(pos)
+      }
+      __syncthreads();
+    }
+    if (tid == 0) Y[(P + 1) / 2] = make_float2(0.f, 0.f);                  // :911 comes after the unpack
+  } else {
+    const int SB = P / 2 + 1;
+    for (int i = tid; i < P; i += nthr) {
+      const int k = i <= P / 2 ? i : P - i;                                // the slave bin this entry of the Hermitian extension comes from
+      const int mi = k + d.shift;
+      const bool ok = mi >= 0 && mi < m_bins && k != (SB + 1) / 2;         // :808, :911
+      float2 x = make_float2(0.f, 0.f);
+      if (ok) {
+        x = cmul(S[mi], Hr[k]);
+        if (k == 0 || 2 * k == P) x.y = 0.f;                               // c2r ignores these imaginary parts
+        if (i > P / 2) x.y = -x.y;
+      }
+      Y[i] = x;
+    }
+  }
+  __syncthreads();
+  return mini_fft<+1>(Y, W, sm, tid, nthr);
+}
+
 __global__ void __launch_bounds__(1024) rmini_ovs(RminiParams p) {
   HIP_DYNAMIC_SHARED(float2, lds)
   const int tid = threadIdx.x, nthr = blockDim.x;
@@ -3458,70 +3520,241 @@ __global__ void __launch_bounds__(1024) rmini_ovs(RminiParams p) {
   __syncthreads();
   const float2* Z = mini_fft<-1>(A, B, p.fwd, tid, nthr);
   float2* S = lds;
-  for (int k = tid; 2 * k <= H; k += nthr) {                               // X_k = (Z_k + conj Z_{H-k})/2 - i/2 W^k (Z_k - conj Z_{H-k})
-    const int kk = H - k;
-    const float2 zk = Z[k], zm = Z[k == 0 ? 0 : kk];
-    const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-    const float2 o = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
-    const float2 t = cmul(o, p.tw_split[k]);
-    const float2 u = cmul(make_float2(o.x, -o.y), p.tw_split[kk]);         // bin H - k: conj(e), conj(o)
-    S[k] = make_float2(e.x + t.x, e.y + t.y);
-    if (kk != k) S[kk] = make_float2(e.x + u.x, u.y - e.y);
-  }
-  __syncthreads();
+  rmini_split(Z, S, p.tw_split, H, tid, nthr);
   const int mask = rq->mask;
-  const int m_bins = H + 1;
   float2* Y = lds + H + 1;
   for (int s = 0; s < p.nslaves; s++) {                                    // (workgroup-uniform control flow throughout)
     if (!((mask >> s) & 1)) continue;
     const MiniParams& sm = p.s[s].m;
-    const int P = sm.N;
-    const ChanDesc d = rq->d[s];
-    const float2* __restrict__ Hr = sm.resp + (size_t)d.row * P;
-    float2* W = Y + P;
-    if (!p.s[s].real_out) {
-      for (int i = tid; i < P; i += nthr) {
-        int t = i - (P + 1) / 2; if (t < 0) t += P;                        // rank from the most negative bin
-        const int u = t - d.t0;
-        const bool ok = (u >= 0) && (u < d.cnt);
-        const int src = d.src0 + d.dir * u;
-        float2 v = make_float2(0.f, 0.f);
-        if (ok) { v = S[src]; if (d.conj) v.y = -v.y; v = cmul(v, Hr[i]); }
-        Y[i] = v;
-      }
-      __syncthreads();
-      if (rq->isb[s]) {                                                    // src/filter.c:895-909: pairs p = 1 .. s_bins/2 - 1 (an odd P leaves its innermost pair alone)
-        for (int q = tid; q < P / 2; q += nthr) {
-          if (q == 0) { Y[0] = make_float2(0.f, 0.f); continue; }
-          const float2 pos = Y[q], neg = Y[P - q];
-          Y[q] = make_float2(pos.x + neg.x, pos.y - neg.y);                // pos + conj(neg)
-          Y[P - q] = make_float2(neg.x - pos.x, neg.y + pos.y);            // neg - conj(pos)
-        }
-        __syncthreads();
-      }
-      if (tid == 0) Y[(P + 1) / 2] = make_float2(0.f, 0.f);                // :911 comes after the unpack
-    } else {
-      const int SB = P / 2 + 1;
-      for (int i = tid; i < P; i += nthr) {
-        const int k = i <= P / 2 ? i : P - i;                              // the slave bin this entry of the Hermitian extension comes from
-        const int mi = k + d.shift;
-        const bool ok = mi >= 0 && mi < m_bins && k != (SB + 1) / 2;       // :808, :911
-        float2 x = make_float2(0.f, 0.f);
-        if (ok) {
-          x = cmul(S[mi], Hr[k]);
-          if (k == 0 || 2 * k == P) x.y = 0.f;                             // c2r ignores these imaginary parts
-          if (i > P / 2) x.y = -x.y;
-        }
-        Y[i] = x;
-      }
-    }
-    __syncthreads();
-    const float2* T = mini_fft<+1>(Y, W, sm, tid, nthr);
-    const int drop = P - sm.olen;
+    const float2* T = rmini_slave(S, Y, p.s[s], rq->d[s], rq->isb[s], H + 1, tid, nthr);
+    const int drop = sm.N - sm.olen;
     float* __restrict__ o = p.out + (size_t)blockIdx.x * p.out_stride + p.s[s].out_off;
     if (p.s[s].real_out) { for (int n = tid; n < sm.olen; n += nthr) o[n] = T[drop + n].x; }
     else { float2* __restrict__ oc = reinterpret_cast<float2*>(o); for (int n = tid; n < sm.olen; n += nthr) oc[n] = T[drop + n]; }
     __syncthreads();                                                       // the next slave overwrites both buffers
+  }
+}
+
+// ------------------------------------------------------------------------------
+// demod_wfm() (src/wfm.c:134-281): the stereo broadcast-FM decoder between a 384 kHz channel's baseband and its 48 kHz PCM.  One
+// workgroup per request, everything in LDS; the discriminator sits in front of rmini_ovs's composite filter (the same forward
+// transform, split and slave rules: mini_fft, rmini_split, rmini_slave), the pilot detector, stereo matrix, de-emphasis and
+// packer behind it.  What differs from rmini_ovs is that the decoder is a recurrence over blocks: per-instance state lives in HBM
+// (WfmState and the last executed block's L composite samples, the M - 1 = L old samples of the next window).
+//   LDS (float2 units): forward A = [0, H), B = [H, 2H) with H = L; the L phases wait in B while A receives the window.
+//   Then S = [0, H] (the master's bins), Y / W = two P-point buffers behind it, the three slaves' olen samples behind those
+//   (mono as floats, pilot and L-R complex), CHZ_WFM_RED doubles of reduction scratch last.  The tail reuses S for the 2 olen
+//   doubles the de-emphasis recurrences walk.
+//   wfm at 20 ms: 122,880 B forward / 92,168 + 19,200 B behind it, + 2,048 B scratch; at 10 ms 61,440 B + 2,048 B.
+// Sums (statistics, pilot amplitude, output energy) are per-thread partials in the reference's own types, added per wavefront and
+// then in wavefront order: a few ulp of a double from the reference's sequential sums.  The de-emphasis recurrences
+// y += rate (gain s - y) are first-order and linear: `deemph_lanes` lanes of wavefront 0 each reduce a run of consecutive samples to
+// an affine map, lane 0 composes the maps, the lanes replay their runs from the right start with the reference's own statement
+// (deemph_lanes = 1: one lane walks the block as the reference does).
+// ------------------------------------------------------------------------------
+#define CHZ_WFM_RED 256
+#define CHZ_WFM_COMPOSITE_RATE 384000.0        // src/wfm.c:22-23: 8 * FULL_SAMPRATE, audio at FULL_SAMPRATE = 48 kHz
+#define CHZ_WFM_AUDIO_RATE 48000.0
+struct WfmState { double phase_memory, foffset, pdeviation, deemph_re, deemph_im, mono_deemph; int squelch_state, channels; };
+struct WfmReq {
+  const float2* bb;       // L complex samples of the channel's baseband (device)
+  double bb_power, n0;
+  double sq_open, sq_close, bandwidth, headroom, deemph_rate, deemph_gain;
+  int inst, stereo_enable, encoding, tail;
+  int pcm_off, pad;       // first byte of this request's PCM row behind p.pcm (a multiple of 4)
+};
+struct WfmStatusK { int frame, mute, squelch_state, channels, pilot_present, pad; double snr, foffset, pdeviation, output_power, gain, subc_amp; };
+struct WfmParams {
+  const WfmReq* req;      // [nreq]
+  WfmState* state;        // [ninst]
+  float* hist;            // [ninst][L]
+  unsigned char* pcm;     // the requests' PCM rows, packed: request r's starts at req[r].pcm_off
+  WfmStatusK* status;     // [nreq]
+  const float2* tw_split; // [N/2 + 1] e^{-2 pi i k / N}
+  MiniParams fwd;         // the N/2-point forward transform
+  RminiSlave s[3];        // mono (REAL), pilot, L-R (COMPLEX); m.resp = the slave's row of instance 0 in [ninst][3][P]
+  ChanDesc d[3];          // their gathers (row: 3 x the instance, filled in per request)
+  int N, olen, out_off, red_off, deemph_lanes;
+  double alpha;           // -expm1(-blocktime)
+};
+
+// sum / max / min of one double per thread over the workgroup, the same value in every thread (blockDim.x is whole wavefronts)
+template <int OP>
+__device__ __forceinline__ double wfm_reduce(double v, double* red, int tid, int nthr) {
+  v = OP == 0 ? wave_sum(v) : OP == 1 ? wave_max(v) : wave_min(v);
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  double r = red[0];
+  for (int w = 1; w < nthr / 64; w++) { const double o = red[w]; r = OP == 0 ? r + o : OP == 1 ? (o > r ? o : r) : (o < r ? o : r); }
+  __syncthreads();
+  return r;
+}
+__device__ __forceinline__ float wfm_cnrmf(float2 v) {                     // cnrmf(): crealf^2 + cimagf^2, each product rounded
+  float a = v.x * v.x, b = v.y * v.y; CHZ_ROUNDED_F32(a); CHZ_ROUNDED_F32(b);
+  return a + b;
+}
+// y += rate (gain s - y) over v[0, n) with stride `stride` doubles, in place (src/wfm.c:241,269); `y0` is the state before the block, the
+// state after it is returned in every thread.  Wavefront 0 works, everybody meets at the barriers.
+__device__ __forceinline__ double wfm_deemph(double* v, int stride, int n, double y0, double rate, double gain, int lanes, double* red, int tid) {
+  const int seg = (n + lanes - 1) / lanes;
+  const int n0 = tid * seg, n1 = n0 + seg < n ? n0 + seg : n;
+  if (lanes > 1) {
+    if (tid < lanes) {                                                     // this run as the affine map y -> a y + b
+      double a = 1.0, b = 0.0;
+      for (int i = n0; i < n1; i++) { b += rate * (gain * v[(size_t)i * stride] - b); a *= 1.0 - rate; }
+      red[2 * tid] = a; red[2 * tid + 1] = b;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      double y = y0;
+      for (int l = 0; l < lanes; l++) { const double a = red[2 * l], b = red[2 * l + 1]; red[2 * l] = y; y = a * y + b; }
+    }
+    __syncthreads();
+    if (tid < lanes) y0 = red[2 * tid];
+    __syncthreads();
+  }
+  if (tid < lanes) {
+    double y = y0;
+    for (int i = n0; i < n1; i++) { y += rate * (gain * v[(size_t)i * stride] - y); v[(size_t)i * stride] = y; }
+    if (n1 == n && n0 < n) red[0] = y;                                      // the lane that holds the last sample
+  }
+  __syncthreads();
+  const double last = red[0];
+  __syncthreads();
+  return last;
+}
+
+__global__ void __launch_bounds__(1024) wfm_ovs(WfmParams p) {
+  HIP_DYNAMIC_SHARED(float2, lds)
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int H = p.N / 2, L = H, olen = p.olen;                             // M = L + 1: the window is L old and L new samples
+  const WfmReq rq = p.req[blockIdx.x];
+  WfmState* __restrict__ stp = p.state + rq.inst;
+  WfmState st = *stp;
+  WfmStatusK* __restrict__ so = p.status + blockIdx.x;
+  double* red = reinterpret_cast<double*>(lds + p.red_off);
+  // ---- power squelch with hysteresis (src/wfm.c:134-151); every thread takes the same decisions
+  const double bw = fabs(rq.bandwidth);
+  const double snr = rq.bb_power / (rq.n0 * bw) - 1;
+  const double fmsnr = 0.0 > snr ? 0.0 : snr;                              // max(0.0, snr)
+  const double gain = (2 * rq.headroom * CHZ_WFM_COMPOSITE_RATE) / bw;     // :193
+  const int sq_max = rq.tail + 1;
+  int sq = st.squelch_state;
+  bool open = true;
+  if (fmsnr >= rq.sq_open || (sq > 0 && snr >= rq.sq_close)) sq = sq_max;
+  else if (--sq > 0) { /* in the tail */ }
+  else open = false;
+  int channels = st.channels ? st.channels : (rq.stereo_enable ? 2 : 1);
+  if (!open) {                                                             // :146-150: no samples, mute; nothing else of the state changes
+    if (tid == 0) {
+      stp->squelch_state = 0; stp->phase_memory = 0;
+      *so = WfmStatusK{1, 1, 0, channels, 0, 0, fmsnr, st.foffset, st.pdeviation, 0.0, gain, 0.0};
+    }
+    return;
+  }
+  // ---- discriminator (:153-161): np = M_1_PI cargf(x[n]), the difference to the sample before wrapped to (-1, 1].  cargf as the
+  // double-precision atan2 rounded to float (what a correctly rounded cargf returns); the L phases wait in B while A receives the window
+  float* Af = reinterpret_cast<float*>(lds);
+  float* ph = reinterpret_cast<float*>(lds + H);
+  float* __restrict__ hist = p.hist + (size_t)rq.inst * L;
+  for (int n = tid; n < L; n += nthr) {
+    Af[n] = hist[n];
+    const float2 v = rq.bb[n];
+    ph[n] = (float)atan2((double)v.y, (double)v.x);
+  }
+  __syncthreads();
+  double psum = 0.0, pmax = 0.0, pmin = 0.0;                               // (:164-165: the peaks start at 0)
+  for (int n = tid; n < L; n += nthr) {
+    const double np = M_1_PI * (double)ph[n];
+    const double prev = n ? M_1_PI * (double)ph[n - 1] : st.phase_memory;
+    const double x = np - prev;
+    const float c = (float)(x > 1 ? x - 2 : x < -1 ? x + 2 : x);
+    Af[L + n] = c;
+    hist[n] = c;                                                           // the new block replaces the history (every thread is past its reads)
+    psum += (double)c;
+    if ((double)c > pmax) pmax = (double)c;
+    if ((double)c < pmin) pmin = (double)c;
+  }
+  st.phase_memory = M_1_PI * (double)ph[L - 1];
+  if (sq == sq_max) {                                                      // :162-185: squelch fully open
+    psum = wfm_reduce<0>(psum, red, tid, nthr); pmax = wfm_reduce<1>(pmax, red, tid, nthr); pmin = wfm_reduce<2>(pmin, red, tid, nthr);
+    const double fo = psum * (CHZ_WFM_COMPOSITE_RATE * 0.5 / L);
+    st.foffset += p.alpha * (fo - st.foffset);
+    const double pp = pmax * (CHZ_WFM_COMPOSITE_RATE * 0.5) - st.foffset, pn = pmin * (CHZ_WFM_COMPOSITE_RATE * 0.5) - st.foffset;
+    st.pdeviation = pp > -pn ? pp : -pn;
+  }
+  __syncthreads();
+  // ---- composite filter (:187-199,223): rmini_ovs's forward transform and split, then the slaves
+  float2* A = lds;
+  float2* B = lds + H;
+  const float2* Z = mini_fft<-1>(A, B, p.fwd, tid, nthr);
+  float2* S = lds;
+  rmini_split(Z, S, p.tw_split, H, tid, nthr);
+  float2* Y = lds + H + 1;
+  float* monoO = reinterpret_cast<float*>(lds + p.out_off);
+  float2* pilO = lds + p.out_off + (olen + 1) / 2;
+  float2* lmrO = pilO + olen;
+  const int no_isb = 0;
+  const int drop = p.s[0].m.N - olen;                                      // (the three slaves are of one size)
+  ChanDesc d = p.d[0]; d.row = 3 * rq.inst;
+  const float2* T = rmini_slave(S, Y, p.s[0], d, no_isb, H + 1, tid, nthr);     // L+R, 50 Hz - 15 kHz, shift 0 (:188)
+  for (int n = tid; n < olen; n += nthr) monoO[n] = T[drop + n].x;
+  __syncthreads();
+  bool pilot = false;
+  double subc_amp = 0.0;
+  if (rq.stereo_enable) {                                                  // :196-210
+    d = p.d[1]; d.row = 3 * rq.inst;
+    T = rmini_slave(S, Y, p.s[1], d, no_isb, H + 1, tid, nthr);            // the pilot spun down from 19 kHz (:199)
+    double acc = 0.0;
+    for (int n = tid; n < olen; n += nthr) { const float2 v = T[drop + n]; pilO[n] = v; acc += (double)wfm_cnrmf(v); }
+    subc_amp = wfm_reduce<0>(acc, red, tid, nthr) / olen;                  // (its barriers also end the reads of T)
+    pilot = subc_amp > 1e-6;
+  }
+  unsigned char* __restrict__ o = p.pcm + rq.pcm_off;
+  double* sv = reinterpret_cast<double*>(lds);                             // S is done with once the last gather has run
+  double energy = 0.0;
+  if (pilot) {                                                             // ---- stereo multiplex (:211-249)
+    channels = 2;
+    d = p.d[2]; d.row = 3 * rq.inst;
+    T = rmini_slave(S, Y, p.s[2], d, no_isb, H + 1, tid, nthr);            // L-R spun down from 38 kHz (:223)
+    for (int n = tid; n < olen; n += nthr) lmrO[n] = T[drop + n];
+    __syncthreads();
+    for (int n = tid; n < olen; n += nthr) {
+      const double pr = pilO[n].x, pi = pilO[n].y;
+      const double nrm = pr * pr + pi * pi;
+      const double cr = (pr * pr - pi * pi) / nrm, ci = (pr * pi + pi * pr) / nrm;       // squared to 38 kHz and normalised (:232)
+      const double lr = lmrO[n].x, li = lmrO[n].y;
+      const double info = 2.0 * (cr * li - ci * lr);                       // 2 Im(conj(subc) lmr) (:233)
+      const double m = monoO[n];
+      sv[2 * n] = m + info; sv[2 * n + 1] = m - info;                      // L, R (:239)
+    }
+    __syncthreads();
+    if (rq.deemph_rate != 0) {                                             // :240-241, the complex recurrence one component at a time
+      st.deemph_re = wfm_deemph(sv, 2, olen, st.deemph_re, rq.deemph_rate, rq.deemph_gain, p.deemph_lanes, red, tid);
+      st.deemph_im = wfm_deemph(sv + 1, 2, olen, st.deemph_im, rq.deemph_rate, rq.deemph_gain, p.deemph_lanes, red, tid);
+    }
+    for (int n = tid; n < olen; n += nthr) {
+      const float2 v = make_float2((float)(sv[2 * n] * gain), (float)(sv[2 * n + 1] * gain));
+      energy += (double)wfm_cnrmf(v);                                      // :244
+      demod_put(o, rq.encoding, 2 * n, v.x); demod_put(o, rq.encoding, 2 * n + 1, v.y);
+    }
+    energy = wfm_reduce<0>(energy, red, tid, nthr) / (2 * olen);           // :247
+  } else {                                                                 // ---- mono (:250-284)
+    channels = 1;
+    for (int n = tid; n < olen; n += nthr) sv[n] = (double)monoO[n];
+    __syncthreads();
+    if (rq.deemph_rate != 0) st.mono_deemph = wfm_deemph(sv, 1, olen, st.mono_deemph, rq.deemph_rate, rq.deemph_gain, p.deemph_lanes, red, tid);
+    for (int n = tid; n < olen; n += nthr) {
+      const double s = sv[n] * gain;
+      energy += s * s;
+      demod_put(o, rq.encoding, n, (float)s);
+    }
+    energy = wfm_reduce<0>(energy, red, tid, nthr) / olen;                 // :281
+  }
+  if (tid == 0) {
+    st.squelch_state = sq; st.channels = channels;
+    *stp = st;
+    *so = WfmStatusK{0, 0, sq, channels, pilot ? 1 : 0, 0, fmsnr, st.foffset, st.pdeviation, energy, gain, subc_amp};
   }
 }
 

@@ -476,4 +476,44 @@ inline int rmini_check_geom(int L, int M, int nslaves, const int* olen, const in
   return 0;
 }
 
+// ---- pooled stereo broadcast-FM decoders (wfm_ovs): demod_wfm()'s geometry for a block time (src/wfm.c:37-101) -------------------------
+// out6: L, N, olen, P, pilot_shift, subc_shift.  Refuses what rmini_check_geom refuses for the composite master (L, M = L + 1) with its
+// three olen-sample slaves, and a 19 or 38 kHz shift that is no multiple of 4 or leaves a remainder (the asserts at :96,101, with
+// compute_tuning's arithmetic, src/radio.c:1175-1199).  Leaves 10 ms and 20 ms blocks.
+#define CHZ_WFM_RED_DOUBLES 256                  // reduction scratch behind the buffers (CHZ_WFM_RED, chz_kernels.h)
+inline int wfm_check_geom(double blocktime, int out6[6], char* why, size_t why_len) {
+  if (!(blocktime > 0) || !(blocktime < 1)) { snprintf(why, why_len, "bad block time %g s", blocktime); return -1; }
+  const double composite = 384000.0, audio = 48000.0;
+  const int L = (int)lrint(composite * blocktime), M = L + 1, olen = (int)lrint(audio * blocktime);
+  const int olens[3] = {olen, olen, olen}, types[3] = {CHZ_IN_REAL, CHZ_IN_COMPLEX, CHZ_IN_COMPLEX};
+  int P[3] = {};
+  const int rc = rmini_check_geom(L, M, 3, olens, types, P, why, why_len);
+  if (rc) return rc;
+  const int N = L + M - 1;
+  const double hzperbin = composite / N;
+  int shift[2];
+  const double freq[2] = {19000.0, 38000.0};
+  for (int k = 0; k < 2; k++) {
+    shift[k] = (int)lrint(freq[k] / hzperbin);
+    const double rem = fma(-(double)shift[k], hzperbin, freq[k]);
+    if (shift[k] % 4 != 0 || rem != 0) {
+      snprintf(why, why_len, "a %g s block puts %g Hz on bin %d of %g Hz with %g Hz left over: the shift must be a multiple of 4 without remainder", blocktime,
+               freq[k], shift[k], hzperbin, rem);
+      return -3;
+    }
+  }
+  if (out6) { out6[0] = L; out6[1] = N; out6[2] = olen; out6[3] = P[0]; out6[4] = shift[0]; out6[5] = shift[1]; }
+  return 0;
+}
+// LDS layout of wfm_ovs in float2 units: the slaves' samples start at out_off, the reduction scratch at red_off; threads as rmini_ovs
+inline void wfm_launch_geom(int N, int P, int olen, int* out_off, int* red_off, size_t* lds, int* threads) {
+  const int H = N / 2;
+  *out_off = H + 1 + 2 * P;
+  const int behind = *out_off + (olen + 1) / 2 + 2 * olen;
+  *red_off = 2 * H > behind ? 2 * H : behind;
+  *lds = sizeof(f2) * (size_t)*red_off + sizeof(double) * CHZ_WFM_RED_DOUBLES;
+  const int q = (H / 4 + 63) / 64 * 64, top = *lds <= 40 * 1024 ? 256 : 1024;
+  *threads = q < 64 ? 64 : (q > top ? top : q);
+}
+
 }  // namespace chz

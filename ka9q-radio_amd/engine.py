@@ -46,6 +46,17 @@ class DemodStatus(C.Structure):
                 ("pll_snr", _d), ("pll_cphase", _d), ("tone_deviation", _d), ("pll_rotations", _i), ("tone_mute", _i)]
 
 
+class WfmParams(C.Structure):
+    """chz_wfm_params: the chan_t members src/wfm.c reads every block (linear amplitudes / power ratios)."""
+    _fields_ = [("stereo_enable", _i), ("encoding", _i), ("squelch_tail", _i),
+                ("squelch_open", _d), ("squelch_close", _d), ("bandwidth", _d), ("headroom", _d), ("deemph_rate", _d), ("deemph_gain", _d)]
+
+
+class WfmStatus(C.Structure):
+    _fields_ = [("frame", _i), ("mute", _i), ("squelch_state", _i), ("channels", _i), ("pilot_present", _i),
+                ("snr", _d), ("foffset", _d), ("pdeviation", _d), ("output_power", _d), ("gain", _d), ("subc_amp", _d)]
+
+
 PCM_S16BE, PCM_S16LE, PCM_F32LE, PCM_F32BE, PCM_MULAW, PCM_ALAW, PCM_F16LE, PCM_F16BE = 0, 1, 2, 3, 4, 5, 6, 7
 
 
@@ -66,6 +77,8 @@ SYMBOLS = [
     "chz_comm_unique_id", "chz_comm_create", "chz_comm_create_file", "chz_comm_destroy", "chz_comm_rank", "chz_comm_world",
     "chz_mini_create", "chz_mini_destroy", "chz_mini_capacity", "chz_mini_add", "chz_mini_release", "chz_mini_set_response", "chz_mini_execute",
     "chz_rmini_create", "chz_rmini_destroy", "chz_rmini_check", "chz_rmini_capacity", "chz_rmini_add", "chz_rmini_release", "chz_rmini_set_response", "chz_rmini_execute",
+    "chz_wfm_check", "chz_wfm_create", "chz_wfm_destroy", "chz_wfm_capacity", "chz_wfm_geometry", "chz_wfm_add", "chz_wfm_release", "chz_wfm_set_params",
+    "chz_wfm_set_response", "chz_wfm_execute",
     "chz_comm_barrier", "chz_comm_allreduce_max", "chz_spectrum_broadcast", "chz_spectrum_exchange_rows", "chz_run_blocks_sharded",
     "chz_comm_create_local", "chz_spectrum_broadcast_local", "chz_set_option",
     "chz_welch_create", "chz_welch_destroy", "chz_welch_set_window", "chz_welch_configure", "chz_welch_poll", "chz_welch_read", "chz_welch_read_async",
@@ -142,6 +155,16 @@ def lib():
         L.chz_rmini_release.argtypes = [_vp, _i]
         L.chz_rmini_set_response.argtypes = [_vp, _i, _i, _vp]
         L.chz_rmini_execute.argtypes = [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.chz_wfm_check.argtypes = [_d]
+        L.chz_wfm_create.argtypes = [C.POINTER(_vp), _d, _i, _i]
+        L.chz_wfm_destroy.argtypes = [_vp]; L.chz_wfm_destroy.restype = None
+        L.chz_wfm_capacity.argtypes = [_vp]
+        L.chz_wfm_geometry.argtypes = [_vp, C.POINTER(_i * 6)]
+        L.chz_wfm_add.argtypes = [_vp]
+        L.chz_wfm_release.argtypes = [_vp, _i]
+        L.chz_wfm_set_params.argtypes = [_vp, _i, C.POINTER(WfmParams)]
+        L.chz_wfm_set_response.argtypes = [_vp, _i, _i, _vp]
+        L.chz_wfm_execute.argtypes = [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]
         L.chz_comm_unique_id.argtypes = [_vp]
         L.chz_comm_create.argtypes = [C.POINTER(_vp), _i, _i, _vp, _i]
         L.chz_comm_create_file.argtypes = [C.POINTER(_vp), _i, _i, C.c_char_p, _i, _d]
@@ -762,6 +785,83 @@ class RealMiniPool:
     def close(self):
         if self._h:
             lib().chz_rmini_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+PCM_SAMPLE_BYTES = {PCM_S16BE: 2, PCM_S16LE: 2, PCM_F32LE: 4, PCM_F32BE: 4, PCM_MULAW: 1, PCM_ALAW: 1, PCM_F16LE: 2, PCM_F16BE: 2}
+
+
+class WfmPool:
+    """Pool of stereo broadcast-FM decoders of one block time (demod_wfm(), src/wfm.c): baseband in, packed PCM and a status record out."""
+
+    def __init__(self, blocktime, capacity, device=0):
+        self._h = _vp()
+        _check(lib().chz_wfm_create(C.byref(self._h), float(blocktime), capacity, device))
+        g = (_i * 6)()
+        _check(lib().chz_wfm_geometry(self._h, C.byref(g)))
+        self.geometry = dict(zip(("L", "N", "olen", "P", "pilot_shift", "subc_shift"), (int(v) for v in g)))
+        self.L, self.N, self.olen, self.P = (self.geometry[k] for k in ("L", "N", "olen", "P"))
+        self.blocktime, self.capacity = float(blocktime), capacity
+        self._enc = {}
+
+    @staticmethod
+    def check(blocktime):
+        """Would a pool of this block time be created?  Raises ChzError with the reason if not; touches no device."""
+        _check(lib().chz_wfm_check(float(blocktime)))
+
+    def add(self):
+        return _check(lib().chz_wfm_add(self._h))
+
+    def release(self, inst):
+        _check(lib().chz_wfm_release(self._h, inst))
+        self._enc.pop(inst, None)
+
+    def set_params(self, inst, params):
+        _check(lib().chz_wfm_set_params(self._h, inst, C.byref(params)))
+        self._enc[inst] = int(params.encoding)
+
+    def set_response(self, inst, slave, resp):
+        r = np.ascontiguousarray(resp, np.complex64).reshape(-1)
+        assert r.shape[0] == self.P
+        _check(lib().chz_wfm_set_response(self._h, inst, slave, r.ctypes.data))
+
+    def execute(self, insts, bb, bb_power, n0, on_device=False, fill=0):
+        """bb: [n][L] complex64 on the host (an array, or a list of n rows of which one may be None: a null row, which the call refuses),
+        or (on_device) n device addresses of L complex samples each, complete before the call.
+        -> (list of n PCM byte arrays, olen * channels samples each, empty for a "no samples" block; WfmStatus array).
+        fill: what the PCM buffers hold before the call (the part of a buffer the block did not write is returned in `self.last_raw`)."""
+        insts = np.ascontiguousarray(insts, np.int32)
+        n = insts.shape[0]
+        if on_device:
+            bp = (_vp * n)(*[int(a) if a else None for a in bb])
+        elif isinstance(bb, (list, tuple)):
+            bb = [None if r is None else np.ascontiguousarray(r, np.complex64).reshape(self.L) for r in bb]
+            bp = (_vp * n)(*[None if r is None else r.ctypes.data for r in bb])
+        else:
+            bb = np.ascontiguousarray(bb, np.complex64).reshape(n, self.L)
+            bp = (_vp * n)(*[bb[i].ctypes.data for i in range(n)])
+        pw = np.ascontiguousarray(bb_power, np.float64).reshape(n)
+        nz = np.ascontiguousarray(n0, np.float64).reshape(n)
+        raw = np.full((n, self.olen * 2 * 4), fill, np.uint8)
+        pp = (_vp * n)(*[raw[i].ctypes.data for i in range(n)])
+        status = (WfmStatus * n)()
+        self.last_raw = raw
+        _check(lib().chz_wfm_execute(self._h, n, insts.ctypes.data, bp, int(bool(on_device)), pw.ctypes.data, nz.ctypes.data, pp, status))
+        pcm = []
+        for i in range(n):
+            nb = 0 if status[i].frame else self.olen * status[i].channels * PCM_SAMPLE_BYTES[self._enc.get(int(insts[i]), PCM_F32LE)]
+            pcm.append(raw[i, :nb].copy())
+        return pcm, status
+
+    def close(self):
+        if self._h:
+            lib().chz_wfm_destroy(self._h)
             self._h = _vp()
 
     def __del__(self):
