@@ -322,7 +322,7 @@ typedef struct chz_demod_params {
 #define CHZ_DEMOD_LINEAR 0
 #define CHZ_DEMOD_FM 1
 typedef struct chz_demod_status {
-  int frame;            /* 0: PCM present (send_output(chan, samples, N, mute)); 1: no samples (send_output(chan, NULL, N, mute)) */
+  int frame;            /* 0: PCM present (send_output(chan, samples, N, mute)); 1: no samples (send_output(chan, NULL, N, mute)); 2: a filter2 bank's pending block (send_output is not called) */
   int mute;
   int squelch_state;
   int pll_lock;         /* chan->pll.lock (linear) */
@@ -364,11 +364,59 @@ int chz_bank_read_pcm_async(chz_engine *e, int bank, int slot, int ch0, int n, v
 #define CHZ_FLAG_MUTE 2
 #define CHZ_FLAG_PLL_LOCK 4
 #define CHZ_FLAG_TONE_MUTE 8
+#define CHZ_FLAG_PENDING 16     /* a filter2 bank's block that did not fire (chz_bank_set_filter2): no frame, the byte holds nothing else */
 int chz_bank_read_pcm_flags_async(chz_engine *e, int bank, int slot, int ch0, int n, void *pcm, unsigned char *flags);
 /* returns once everything chz_bank_read_pcm_async / _flags_async has enqueued for `slot` so far has landed in the host buffers --
    without waiting for later blocks already handed to the demodulator stream (a double-buffered host loop waits for block j-1
    here while block j runs) */
 int chz_bank_pcm_wait(chz_engine *e, int bank, int slot);
+
+/* ---- filter2 resident on the device: the channel's private second filter of downconvert() (src/radio.c:1503-1513, created at
+ * :1572-1594; presets cwu / cwl with filter2 = 4, isb with filter2 = 1, share/presets.conf:204,223,297) as a stage of the block pipeline.
+ * For a COMPLEX-output bank with tuning the engine runs a second overlap-save filter per channel behind every whole-bank channel
+ * launch (chz_bank_execute, chz_step, chz_run_blocks), in block order on the demodulator stream, directly in front of the bank's
+ * demodulators (kernel f2_ovs, one workgroup per channel, the transforms and gather rules of chz_mini_*).  It reads what the channel
+ * kernel left in the slot's output image -- the samples behind the fine-tuning rotator (:1499-1501) --, the demodulators read ITS output,
+ * and the slot's bb_power (chz_bank_read_power) is that of its output (:1515-1520).  Nothing travels to the host in between.
+ *   blocking = chan->filter2.blocking >= 1; L2 = blocking * olen; M2 as given, 0 = radiod's own round2(2 L2) - L2 + 1 (:1578-1579);
+ *   N2 = L2 + M2 - 1.  Refused, here and by chz_bank_filter2_check and nowhere else, is what chz_mini_create refuses: N2 outside
+ *   8..8192 or with a prime factor above 13.
+ * ONE phase per bank: block job0 is the first of a cycle and block j FIRES when (j - job0 + 1) % blocking == 0; a caller that needs
+ * another phase uses another bank (no per-channel phase).  There is no drop-in entry point: filter.h callers create filter2
+ * themselves and keep going through chz_mini_*.
+ *   every block   the channel's olen new samples join its window (device memory, [capacity][N2]; zeros at first, as
+ *                 create_filter_input leaves them, src/filter.c:244,259)
+ *   firing block  transform of the N2-sample window (M2 - 1 old samples, L2 new ones), gather with shift 0 x response (:1511), ISB
+ *                 unpacking where the channel's flag is set, zeroed Nyquist bin, backward transform, the last L2 samples to the
+ *                 slot's filter2 image; bb_power = mean |y|^2 (float products, double sum); the demodulators then run on L2 samples
+ *                 with the bank's unchanged block time (demod_linear / demod_fm see sampcount = L2 with the global Blocktime)
+ *   pending block the reference's `continue` (:1509-1510): no demodulator launch; bb_power repeats the last firing block's value
+ *                 (0 before the first); for channels with a demodulator the n0 smoother of :1468-1474, which sits in front of the
+ *                 `continue`, takes its step; the slot's flag byte is CHZ_FLAG_PENDING, its status record has frame = 2 (send_output
+ *                 is not called) and the smoothed n0, the PCM is left alone
+ * A filter2 image exists per spectrum slot that can fire: CHZ_ND / gcd(blocking, CHZ_ND) of them.  Only whole-bank launches step the
+ * stage: chz_bank_execute_range never touches a window.  Narrowband analysers attached to the bank keep reading the first filter's
+ * output.  The demodulators' block length becomes L2 everywhere: the 10240-sample limit, chz_bank_set_pcm_stride's range (L2 .. 8 L2)
+ * and default, the PCM fit check; chz_bank_set_demod's `job` counts as the cycle it falls in (name the first block of a cycle).  Hence chz_bank_set_filter2 is
+ * refused once the bank has demodulators or a fixed PCM row size, and on REAL-output banks and banks without tuning;
+ * chz_bank_write_block / chz_bank_demod are refused on such a bank, chz_run_blocks mode 1 too (-5).  The channel kernel's AGC-peak
+ * epilogue is off; the demodulator takes its own first look at the block. */
+int chz_bank_filter2_check(int olen, int blocking, int M2);      /* would chz_bank_set_filter2 take this geometry? 0, or < 0 and chz_last_error(); touches no device */
+/* job0 has not been enqueued yet.  Drains the engine once, like other feature switches. */
+int chz_bank_set_filter2(chz_engine *e, int bank, unsigned job0, int blocking, int M2);
+int chz_bank_filter2_geometry(chz_engine *e, int bank, int out3[3]);                       /* L2, M2, N2 */
+/* N2 complex per channel, as set_filter leaves it (:1591-1594); zeros until set.  In stream order from the next block enqueued; edits
+ * of up to 8 MB do not drain */
+int chz_bank_set_filter2_responses(chz_engine *e, int bank, int ch0, int n, const float *resp);
+/* chan->filter2.out.isb (:1569,1586): one byte per channel, non-zero = on; in stream order like the responses */
+int chz_bank_set_filter2_isb(chz_engine *e, int bank, int ch0, int n, const unsigned char *flags);
+/* what set_channel_filter's delete and re-create do (:1570-1583): the channels' windows are zeros from block `job` on, which must be
+ * the next block to be enqueued and the first of a cycle (the bank has one phase), else the call is refused */
+int chz_bank_filter2_reset(chz_engine *e, int bank, unsigned job, int ch0, int n);
+/* L2 complex per channel of the block that fired on `slot`; an error if that slot's last block was pending.  Synchronous /
+ * asynchronous on the demodulator stream (completion: chz_sync) */
+int chz_bank_filter2_read(chz_engine *e, int bank, int slot, int ch0, int n, float *host);
+int chz_bank_filter2_read_async(chz_engine *e, int bank, int slot, int ch0, int n, float *host);
 
 /* ---- small inline masters: radiod's filter2 (src/radio.c:1572-1594: a private COMPLEX master of N = round2(2*blocksize)
  * points with one same-size COMPLEX slave, run inline by the channel thread; share/presets.conf:204,223,297).  A pool holds

@@ -148,7 +148,26 @@ struct Bank {
   unsigned bb_newest = 0;                         // the newest block whose append has been issued (job0 - 1 of the first attach: none yet)
   hipEvent_t bb_done = nullptr;                   // on the polls' stream behind the latest poll of this bank's analysers
   int bb_busy = 0; unsigned bb_guard = 0;         // an unfinished poll may still read ring samples that the append of a block after bb_guard overwrites
+  // filter2 resident on the device (chz_bank_set_filter2, chz_filter2.inc; kernel f2_ovs): behind every whole-bank channel launch, in
+  // block order on the demodulator stream, in front of the bank's demodulators -- which then read its output image, f2_L samples a time
+  int f2_B = 0, f2_L = 0, f2_M = 0, f2_N = 0;     // blocking (0 = off), L2 = B olen, M2, N2 = L2 + M2 - 1
+  unsigned f2_job0 = 0;                           // block f2_job0 is the first of a cycle
+  float2* f2_win = nullptr;                       // [cap][N2] the channels' windows
+  float2* f2_resp = nullptr;                      // [cap][N2]
+  float2* f2_out = nullptr;                       // [f2_nimg][cap][L2]: one image per spectrum slot that can fire
+  float2* f2_tw = nullptr;                        // [N2]
+  unsigned char* f2_isb = nullptr;                // [cap]
+  double* f2_last = nullptr;                      // [cap] bb_power of the last firing block
+  int f2_img[CHZ_ND] = {-1, -1, -1, -1}; int f2_nimg = 0;
+  bool f2_fired[CHZ_ND] = {false, false, false, false};   // the slot's latest whole-bank block fired (what chz_bank_filter2_read may return)
+  bool f2_seen = false; unsigned f2_newest = 0;   // the newest whole-bank block issued since chz_bank_set_filter2
+  MiniParams f2_m{}; ChanDesc f2_d{};
+  // edits (responses, ISB flags) travel through a pinned staging buffer onto the demodulator stream: in stream order, no drain
+  char* f2_stage = nullptr; size_t f2_stage_bytes = 0; hipEvent_t f2_stage_ev = nullptr; bool f2_stage_busy = false;
 };
+// what the bank's demodulators see as one block: filter2 hands them f2_L samples whenever it fires, numbered by its cycles
+static inline int bank_dm_len(const Bank& b) { return b.f2_B > 0 ? b.f2_L : b.olen; }
+static inline unsigned bank_dm_job(const Bank& b, unsigned job) { return b.f2_B > 0 ? (unsigned)(job - b.f2_job0) / (unsigned)b.f2_B : job; }
 
 // A lane = one HIP stream + its own intermediate buffer.  Consecutive blocks go to
 // consecutive lanes, so block j+1's forward transform overlaps block j's tail and channel
@@ -335,6 +354,11 @@ static void free_bank(Bank& b) {
     b.ev_bank[s] = b.ev_tail[s] = b.ev_pcm[s] = b.ev_pcmgo[s] = nullptr; b.tail_used[s] = false; b.pcm_copying[s] = false;
   }
   hipFree(b.bb); b.bb = nullptr; b.bb_h.clear(); b.bb_n = 0; b.bb_busy = 0;
+  hipFree(b.f2_win); hipFree(b.f2_resp); hipFree(b.f2_out); hipFree(b.f2_tw); hipFree(b.f2_isb); hipFree(b.f2_last);
+  b.f2_win = b.f2_resp = b.f2_out = b.f2_tw = nullptr; b.f2_isb = nullptr; b.f2_last = nullptr; b.f2_B = 0; b.f2_nimg = 0; b.f2_seen = false;
+  if (b.f2_stage) (void)hipHostFree(b.f2_stage);
+  if (b.f2_stage_ev) (void)hipEventDestroy(b.f2_stage_ev);
+  b.f2_stage = nullptr; b.f2_stage_bytes = 0; b.f2_stage_ev = nullptr; b.f2_stage_busy = false;
   if (b.bb_done) (void)hipEventDestroy(b.bb_done);
   b.bb_done = nullptr;
   for (int s = 0; s < CHZ_ND; s++) { if (b.ev_bb[s]) (void)hipEventDestroy(b.ev_bb[s]); b.ev_bb[s] = nullptr; b.bb_rec[s] = false; }
@@ -1213,7 +1237,7 @@ static int enqueue_bank(chz_engine* e, int bank, unsigned job, Instr* in, int ch
   // the AGC's first look at the block rides in the channel kernel's epilogue when the rows pass through LDS anyway (large launches) and the
   // lane-per-channel demodulator follows
   // (only when somebody will use them: linear channels outside the coherent modes, served by the lane-per-channel demodulator)
-  const bool peaks = b.agc_peak && whole_bank && c.stage && !b.g.any && !b.out_real && (c.fine || c.power) && b.dm_on > 0 && b.dm_auto &&
+  const bool peaks = b.agc_peak && b.f2_B == 0 && whole_bank && c.stage && !b.g.any && !b.out_real && (c.fine || c.power) && b.dm_on > 0 && b.dm_auto &&
                      b.dm_lin > b.dm_pll_lin && (e->demod_wave == 0 || (e->demod_wave < 0 && b.dm_lin >= 65536));
   if (peaks) { c.agc_peak = b.agc_peak + so; int sps = (int)std::rint(b.olen * .002 / b.dm_blocktime); c.agc_sps = sps < 1 ? 1 : sps; }
   if (whole_bank) b.agc_peak_valid[slot] = peaks;
@@ -1245,27 +1269,49 @@ static int enqueue_bank(chz_engine* e, int bank, unsigned job, Instr* in, int ch
     mark(in, st, 3, false);
   }
   // the linear demodulators of this bank, in block order on the demodulator stream.  Only whole-bank
-  // launches feed them (a single-channel re-run of the drop-in's miss path does not advance anybody's AGC).
-  if (b.dm_on > 0 && b.dm_auto && whole_bank) {
+  // launches feed them (a single-channel re-run of the drop-in's miss path does not advance anybody's AGC) -- and the bank's
+  // filter2 stage in front of them, whose windows a re-run must not touch either.
+  const bool f2 = b.f2_B > 0 && whole_bank;
+  const bool fire = f2 && f2_phase(job, b.f2_job0, b.f2_B) == b.f2_B - 1;
+  const bool demod = b.dm_on > 0 && b.dm_auto && whole_bank && (!f2 || fire);       // a pending block: the reference's `continue`, src/radio.c:1509-1510
+  if (f2 || demod) {
     hipStream_t ts = (in && in->on) ? st : e->tail;
     if (ts != st) {
       HIPOK(hipEventRecord(b.ev_bank[slot], st));
       HIPOK(hipStreamWaitEvent(ts, b.ev_bank[slot], 0));
     }
     if (b.pcm_copying[slot]) HIPOK(hipStreamWaitEvent(ts, b.ev_pcm[slot], 0));      // the slot's PCM of four blocks ago is still travelling
-    DemodParams d{};
-    d.in = bank_out(b, slot); d.power = b.power + so; d.n0 = b.n0 + so; d.chan = b.dm_chan; d.state = b.dm_state; d.ext = b.dm_ext;
-    d.status = b.dm_status + so; d.flags = b.dm_flags + so; d.pcm = b.dm_pcm + so * (size_t)b.pcm_stride; d.ch0 = 0; d.nch = n; d.olen = b.olen;
-    d.pcm_stride = b.pcm_stride; d.job = job; d.blocktime = b.dm_blocktime; d.power_alpha = 0.10;      // Power_alpha, src/radio.c:72
-    d.lin_pll = b.dm_pll_lin > 0; d.fm_pll = b.dm_fm_pll > 0; d.fm_tone = b.dm_fm_tone > 0;
-    d.mix = (d.lin_pll || d.fm_pll || d.fm_tone) ? b.dm_mix : nullptr;
-    demod_paths(e, b, d);
-    if (b.agc_peak && d.lin_lanes) {       // the AGC's first look: left by the channel kernel and, for coherent-mode channels, by pll_lanes
-      d.agc_peak = b.agc_peak + so; d.peak_chan = b.agc_peak_valid[slot] ? 1 : 0; d.peak_pll = (d.lin_pll && d.mix != nullptr) ? 1 : 0;
+    const float2* dm_in = bank_out(b, slot);
+    if (f2) {
+      if ((int)(job - b.f2_job0) < 0) return fail(-1, "block %u precedes the first block of the bank's filter2 (%u)", job, b.f2_job0);
+      if (fire && b.f2_img[slot] < 0) return fail(-4, "slot %d has no filter2 image", slot);      // (cannot happen: chz_bank_set_filter2 gives every firing slot one)
+      F2Params q{};
+      q.in = bank_out(b, slot); q.win = b.f2_win; q.resp = b.f2_resp; q.isb = b.f2_isb; q.power = b.power + so; q.last_power = b.f2_last;
+      q.out = b.f2_img[slot] >= 0 ? b.f2_out + (size_t)b.f2_img[slot] * b.cap * b.f2_L : nullptr;
+      if (b.dm_chan) { q.chan = b.dm_chan; q.state = b.dm_state; q.status = b.dm_status + so; q.flags = b.dm_flags + so; q.n0 = b.n0 + so; }
+      q.power_alpha = 0.10; q.d = b.f2_d; q.m = b.f2_m; q.olen = b.olen; q.L = b.f2_L; q.blocking = b.f2_B; q.job = job; q.job0 = b.f2_job0;
+      launch_f2(ts, q, n);
+      dm_in = q.out;
+      b.f2_fired[slot] = fire;
+      unsigned cur = __atomic_load_n(&b.f2_newest, __ATOMIC_RELAXED);      // (issued in block order: enqueue_step's turn)
+      if (!b.f2_seen || (int)(job - cur) > 0) __atomic_store_n(&b.f2_newest, job, __ATOMIC_RELAXED);
+      b.f2_seen = true;
     }
-    mark(in, ts, 6, true);
-    if (launch_demod(ts, d, IN_E0(in), IN_E1(in))) return fail(-4, "the demodulator kernel refuses blocks of %d samples", b.olen);
-    mark(in, ts, 6, false);
+    if (demod) {
+      DemodParams d{};
+      d.in = dm_in; d.power = b.power + so; d.n0 = b.n0 + so; d.chan = b.dm_chan; d.state = b.dm_state; d.ext = b.dm_ext;
+      d.status = b.dm_status + so; d.flags = b.dm_flags + so; d.pcm = b.dm_pcm + so * (size_t)b.pcm_stride; d.ch0 = 0; d.nch = n; d.olen = bank_dm_len(b);
+      d.pcm_stride = b.pcm_stride; d.job = bank_dm_job(b, job); d.blocktime = b.dm_blocktime; d.power_alpha = 0.10;      // Power_alpha, src/radio.c:72
+      d.lin_pll = b.dm_pll_lin > 0; d.fm_pll = b.dm_fm_pll > 0; d.fm_tone = b.dm_fm_tone > 0;
+      d.mix = (d.lin_pll || d.fm_pll || d.fm_tone) ? b.dm_mix : nullptr;
+      demod_paths(e, b, d);
+      if (b.agc_peak && d.lin_lanes) {       // the AGC's first look: left by the channel kernel and, for coherent-mode channels, by pll_lanes
+        d.agc_peak = b.agc_peak + so; d.peak_chan = b.agc_peak_valid[slot] ? 1 : 0; d.peak_pll = (d.lin_pll && d.mix != nullptr) ? 1 : 0;
+      }
+      mark(in, ts, 6, true);
+      if (launch_demod(ts, d, IN_E0(in), IN_E1(in))) return fail(-4, "the demodulator kernel refuses blocks of %d samples", d.olen);
+      mark(in, ts, 6, false);
+    }
     if (ts != st) { HIPOK(hipEventRecord(b.ev_tail[slot], ts)); b.tail_used[slot] = true; __atomic_store_n(&e->tail_issued, 1, __ATOMIC_RELAXED); }
   }
   return 0;
@@ -1596,7 +1642,8 @@ static int read_doubles(chz_engine* e, int bank, const double* base, int slot, i
   if (slot < 0 || slot >= CHZ_ND || !host) return fail(-1, "bad argument");
   Bank& b = e->banks[(size_t)bank];
   if (!base) return fail(-1, "%s", what);
-  hipStream_t st = slot_stream(e, slot);
+  // a filter2 bank's bb_power is written by its filter2 stage, on the demodulator stream
+  hipStream_t st = (base == b.power && b.f2_B > 0) ? e->tail : slot_stream(e, slot);
   HIPOK(hipMemcpyAsync(host, base + (size_t)slot * b.cap + ch0, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
   if (wait) HIPOK(hipStreamSynchronize(st));
   return 0;
@@ -1665,6 +1712,16 @@ int chz_bank_set_beam(chz_engine* e, int bank, int ch0, int n, const double* ab,
   return after_edit(e, b, ch0, n);
 }
 // demod_linear()'s per-block work for channels [ch0, ch0+n) from block `job` on
+// the events that tie a slot's lane to the demodulator stream (the bank's demodulators and its filter2 stage share them)
+static int bank_tail_events(Bank& b) {
+  for (int s = 0; s < CHZ_ND; s++) {
+    if (!b.ev_bank[s]) HIPOK(hipEventCreateWithFlags(&b.ev_bank[s], hipEventDisableTiming));
+    if (!b.ev_tail[s]) HIPOK(hipEventCreateWithFlags(&b.ev_tail[s], hipEventDisableTiming));
+    if (!b.ev_pcm[s]) HIPOK(hipEventCreateWithFlags(&b.ev_pcm[s], hipEventDisableTiming));
+    if (!b.ev_pcmgo[s]) HIPOK(hipEventCreateWithFlags(&b.ev_pcmgo[s], hipEventDisableTiming));
+  }
+  return 0;
+}
 int chz_bank_set_demod(chz_engine* e, int bank, unsigned job, int ch0, int n, const chz_demod_params* p, double blocktime) {
   BANK_CHECK(e, bank, ch0, n);
   if (!p || !(blocktime > 0)) return fail(-1, "bad argument");
@@ -1672,13 +1729,15 @@ int chz_bank_set_demod(chz_engine* e, int bank, unsigned job, int ch0, int n, co
   if (b.out_real) return fail(-1, "the linear demodulator follows COMPLEX-output channels");
   if (!b.power || !b.n0 || b.noise_samprate <= 0.0)
     return fail(-1, "the demodulator needs the channel's bb_power and noise estimate: call chz_bank_set_tuning and chz_bank_enable_noise first");
-  if (b.olen > 10240) return fail(-3, "the demodulator kernel keeps a block in LDS: at most 10240 samples per block (bank has %d)", b.olen);
-  if (!b.pcm_stride) b.pcm_stride = b.olen * 8;
+  const int dlen = bank_dm_len(b);          // a filter2 bank hands its demodulators L2 samples at a time
+  if (dlen > 10240) return fail(-3, "the demodulator kernel keeps a block in LDS: at most 10240 samples per block (bank has %d)", dlen);
+  if (!b.pcm_stride) b.pcm_stride = dlen * 8;
+  job = bank_dm_job(b, job);
   bool need_ext = false, need_fm_mix = false;
   for (int i = 0; i < n; i++) {
     const chz_demod_params& q = p[i];
     if (q.channels < 0 || q.channels > 2 || q.encoding < CHZ_PCM_S16BE || q.encoding > CHZ_PCM_F16BE) return fail(-1, "bad demodulator parameters for channel %d", ch0 + i);
-    if (q.channels * b.olen * ((q.encoding == CHZ_PCM_MULAW || q.encoding == CHZ_PCM_ALAW) ? 1 :
+    if (q.channels * dlen * ((q.encoding == CHZ_PCM_MULAW || q.encoding == CHZ_PCM_ALAW) ? 1 :
                                (q.encoding == CHZ_PCM_S16BE || q.encoding == CHZ_PCM_S16LE || q.encoding == CHZ_PCM_F16LE || q.encoding == CHZ_PCM_F16BE) ? 2 : 4) > b.pcm_stride)
       return fail(-1, "channel %d's PCM does not fit the bank's %d-byte rows (chz_bank_set_pcm_stride)", ch0 + i, b.pcm_stride);
     if (q.channels > 0 && !(q.samprate > 0 && q.headroom > 0 && q.bandwidth > 0 && std::isfinite(q.shift) && q.gain > 0))
@@ -1703,12 +1762,7 @@ int chz_bank_set_demod(chz_engine* e, int bank, unsigned job, int ch0, int n, co
     HIPOK(hipMalloc((void**)&b.dm_status, sizeof(DemodStatus) * cap * CHZ_ND)); HIPOK(hipMemset(b.dm_status, 0, sizeof(DemodStatus) * cap * CHZ_ND));
     HIPOK(hipMalloc((void**)&b.dm_flags, cap * CHZ_ND)); HIPOK(hipMemset(b.dm_flags, 0, cap * CHZ_ND));
     HIPOK(hipMalloc((void**)&b.dm_pcm, (size_t)b.pcm_stride * cap * CHZ_ND)); HIPOK(hipMemset(b.dm_pcm, 0, (size_t)b.pcm_stride * cap * CHZ_ND));
-    for (int s = 0; s < CHZ_ND; s++) {
-      HIPOK(hipEventCreateWithFlags(&b.ev_bank[s], hipEventDisableTiming));
-      HIPOK(hipEventCreateWithFlags(&b.ev_tail[s], hipEventDisableTiming));
-      HIPOK(hipEventCreateWithFlags(&b.ev_pcm[s], hipEventDisableTiming));
-      HIPOK(hipEventCreateWithFlags(&b.ev_pcmgo[s], hipEventDisableTiming));
-    }
+    { int r = bank_tail_events(b); if (r) return r; }
     HIPOK(hipDeviceSynchronize());
     DemodChan z; memset(&z, 0, sizeof z);
     b.dm_chan_h.assign(cap, z);
@@ -1730,8 +1784,8 @@ int chz_bank_set_demod(chz_engine* e, int bank, unsigned job, int ch0, int n, co
     drop_graph(e);
   }
   if ((need_ext || need_fm_mix) && !b.dm_mix && !e->opt_pll_lane0) {      // (A/B knob: round 2's one-lane-per-channel loops inside the demodulator kernel)
-    HIPOK(hipMalloc((void**)&b.dm_mix, sizeof(float2) * (size_t)b.cap * b.olen));
-    HIPOK(hipMemset(b.dm_mix, 0, sizeof(float2) * (size_t)b.cap * b.olen));
+    HIPOK(hipMalloc((void**)&b.dm_mix, sizeof(float2) * (size_t)b.cap * dlen));
+    HIPOK(hipMemset(b.dm_mix, 0, sizeof(float2) * (size_t)b.cap * dlen));
     HIPOK(hipDeviceSynchronize());
     drop_graph(e);
   }
@@ -1775,7 +1829,7 @@ int chz_bank_set_demod(chz_engine* e, int bank, unsigned job, int ch0, int n, co
     const double f = q.shift / q.samprate;
     if (!o.init) { o.init = true; o.freq = 0.0; o.phase0 = 0.0; o.job0 = job; }
     if (f != o.freq) {
-      const double g = (double)(job - o.job0) * (double)b.olen;
+      const double g = (double)(job - o.job0) * (double)dlen;
       double hi = g * o.freq, lo = std::fma(g, o.freq, -hi);
       hi -= std::rint(hi);
       o.phase0 = frac1(o.phase0 + hi + lo); o.job0 = job; o.freq = f;
@@ -1815,6 +1869,7 @@ int chz_bank_write_block(chz_engine* e, int bank, int slot, int ch0, int n, cons
   Bank& b = e->banks[(size_t)bank];
   if (b.out_real) return fail(-1, "the demodulators follow COMPLEX-output channels");
   if (!b.dm_chan) return fail(-1, "bank has no demodulator: call chz_bank_set_demod first");
+  if (b.f2_B) return fail(-1, "the bank runs filter2 on the device: its demodulators read filter2's output, not the slot's image");
   HIPOK(hipSetDevice(e->device));
   const size_t so = (size_t)slot * b.cap + ch0;
   HIPOK(hipMemcpyAsync(bank_out(b, slot) + (size_t)ch0 * b.olen, samples, sizeof(float2) * (size_t)n * b.olen, hipMemcpyHostToDevice, e->tail));
@@ -1836,6 +1891,7 @@ int chz_bank_demod(chz_engine* e, int bank, unsigned job, int slot) {
   if (slot < 0 || slot >= CHZ_ND) return fail(-1, "bad slot");
   Bank& b = e->banks[(size_t)bank];
   if (!b.dm_chan || b.dm_on <= 0) return fail(-1, "bank has no demodulator: call chz_bank_set_demod first");
+  if (b.f2_B) return fail(-1, "the bank runs filter2 on the device: its demodulators follow filter2 in the block pipeline");
   HIPOK(hipSetDevice(e->device));
   const size_t so = (size_t)slot * b.cap;
   DemodParams d{};
@@ -1854,7 +1910,7 @@ int chz_bank_demod(chz_engine* e, int bank, unsigned job, int slot) {
 int chz_bank_pcm_stride(chz_engine* e, int bank) {
   BANK_CHECK(e, bank, 0, 0);
   const Bank& b = e->banks[(size_t)bank];
-  return b.pcm_stride ? b.pcm_stride : b.olen * 8;
+  return b.pcm_stride ? b.pcm_stride : bank_dm_len(b) * 8;
 }
 // rows of exactly the size the bank's encodings need (480 B for 12 kHz mono S16) make the device-to-host copy of a block's
 // PCM one contiguous transfer of only the bytes that matter; before the first chz_bank_set_demod
@@ -1863,7 +1919,8 @@ int chz_bank_set_pcm_stride(chz_engine* e, int bank, int bytes) {
   BANK_CHECK(e, bank, 0, 0);
   Bank& b = e->banks[(size_t)bank];
   if (b.dm_chan) return fail(-1, "the PCM row size is fixed once demodulators exist");
-  if (bytes < b.olen || bytes > 8 * b.olen || (bytes & 3)) return fail(-1, "PCM rows hold %d..%d bytes, a multiple of 4", b.olen, 8 * b.olen);
+  const int dlen = bank_dm_len(b);
+  if (bytes < dlen || bytes > 8 * dlen || (bytes & 3)) return fail(-1, "PCM rows hold %d..%d bytes, a multiple of 4", dlen, 8 * dlen);
   b.pcm_stride = bytes;
   return 0;
 }
@@ -2011,7 +2068,7 @@ static int enqueue_step(chz_engine* e, unsigned job, Instr* in, NotchTurn* turn 
   int r = enqueue_forward(e, job, in, turn, seq, capture_first, capturing);
   if (r) return r;
   bool demod = false;
-  for (const Bank& b : e->banks) demod = demod || b.dm_on > 0 || b.bb_n > 0;      // (or feeds baseband rings: enqueue_bb_append)
+  for (const Bank& b : e->banks) demod = demod || b.dm_on > 0 || b.bb_n > 0 || b.f2_B > 0;      // (or feeds baseband rings: enqueue_bb_append; or steps filter2 windows)
   if (demod && turn) {                // what goes to the demodulator stream is issued in block order
     while (turn->next_tail.load(std::memory_order_acquire) != seq) {
       if (turn->abort.load(std::memory_order_relaxed)) return fail(-6, "another issuing thread failed");
@@ -2059,7 +2116,7 @@ int chz_run_blocks(chz_engine* e, unsigned job0, int nblocks, int mode, int inst
   if (!e || nblocks < 0) return fail(-1, "bad argument");
   if (mode == 1)
     for (const Bank& b : e->banks)
-      if (b.fine || b.dm_on || b.bb_n) return fail(-5, "graph replay bakes the block number into the captured launches; fine-tuned and demodulated banks and banks with attached spectrum analysers need eager mode");
+      if (b.fine || b.dm_on || b.bb_n || b.f2_B) return fail(-5, "graph replay bakes the block number into the captured launches; fine-tuned and demodulated banks, banks with filter2 and banks with attached spectrum analysers need eager mode");
   HIPOK(hipSetDevice(e->device));
   { int r = sync_all(e); if (r) return r; }
   e->input_pending = false;                       // everything written so far is visible to every lane now
@@ -2221,6 +2278,7 @@ int chz_run_blocks(chz_engine* e, unsigned job0, int nblocks, int mode, int inst
 
 #include "chz_comm.inc"
 #include "chz_mini.inc"
+#include "chz_filter2.inc"
 #include "chz_rmini.inc"
 #include "chz_wfm.inc"
 #include "chz_welch.inc"

@@ -3365,6 +3365,35 @@ __device__ __forceinline__ float2* mini_fft(float2* a, float2* b, const MiniPara
   return a;        // where the result is
 }
 
+// gather x response into the slave's bins (FFT order), exactly as chan_ifft does for a COMPLEX master, ISB unpacking
+// (src/filter.c:895-909) and the zeroed Nyquist bin (:911, after the unpack): X[P] -> Y[P], H the slave's response
+__device__ __forceinline__ void mini_gather(const float2* X, float2* Y, const float2* __restrict__ H, const ChanDesc& d, int isb, int P,
+                                            int tid, int nthr) {
+  for (int i = tid; i < P; i += nthr) {
+    int t = i - (P + 1) / 2; if (t < 0) t += P;            // rank from the most negative bin
+    const int u = t - d.t0;
+    const bool ok = (u >= 0) && (u < d.cnt);
+    int src = d.src0 + d.dir * u;
+    if (d.wrap && src >= d.wrap) src -= d.wrap;
+    float2 v = make_float2(0.f, 0.f);
+    if (ok) { v = X[src]; if (d.conj) v.y = -v.y; v = cmul(v, H[i]); }
+    Y[i] = v;
+  }
+  __syncthreads();
+  if (isb) {                                               // src/filter.c:895-909
+    for (int q = tid; q <= P / 2; q += nthr) {
+      if (q == 0) { Y[0] = make_float2(0.f, 0.f); continue; }
+      if (2 * q >= P) continue;
+      const float2 pos = Y[q], neg = Y[P - q];
+      Y[q] = make_float2(pos.x + neg.x, pos.y - neg.y);          // pos + conj(neg)
+      Y[P - q] = make_float2(neg.x - pos.x, neg.y + pos.y);      // neg - conj(pos)
+    }
+    __syncthreads();
+  }
+  if (tid == 0) Y[(P + 1) / 2] = make_float2(0.f, 0.f);     // :911 comes after the unpack
+  __syncthreads();
+}
+
 __global__ void __launch_bounds__(256) mini_ovs(MiniParams p) {
   HIP_DYNAMIC_SHARED(float2, lds)
   const int tid = threadIdx.x, nthr = blockDim.x;
@@ -3377,36 +3406,100 @@ __global__ void __launch_bounds__(256) mini_ovs(MiniParams p) {
   __syncthreads();
   float2* X = mini_fft<-1>(A, B, p, tid, nthr);            // master spectrum, natural order
   float2* Y = (X == A) ? B : A;
-  // gather x response into the slave's bins (FFT order), exactly as chan_ifft does for a COMPLEX master
-  const float2* __restrict__ H = p.resp + (size_t)rq.d.row * N;
-  const int P = N;
-  for (int i = tid; i < P; i += nthr) {
-    int t = i - (P + 1) / 2; if (t < 0) t += P;            // rank from the most negative bin
-    const int u = t - rq.d.t0;
-    const bool ok = (u >= 0) && (u < rq.d.cnt);
-    int src = rq.d.src0 + rq.d.dir * u;
-    if (rq.d.wrap && src >= rq.d.wrap) src -= rq.d.wrap;
-    float2 v = make_float2(0.f, 0.f);
-    if (ok) { v = X[src]; if (rq.d.conj) v.y = -v.y; v = cmul(v, H[i]); }
-    Y[i] = v;
-  }
-  __syncthreads();
-  if (rq.isb) {                                            // src/filter.c:895-909
-    for (int q = tid; q <= P / 2; q += nthr) {
-      if (q == 0) { Y[0] = make_float2(0.f, 0.f); continue; }
-      if (2 * q >= P) continue;
-      const float2 pos = Y[q], neg = Y[P - q];
-      Y[q] = make_float2(pos.x + neg.x, pos.y - neg.y);          // pos + conj(neg)
-      Y[P - q] = make_float2(neg.x - pos.x, neg.y + pos.y);      // neg - conj(pos)
-    }
-    __syncthreads();
-  }
-  if (tid == 0) Y[(P + 1) / 2] = make_float2(0.f, 0.f);     // :911 comes after the unpack
-  __syncthreads();
+  mini_gather(X, Y, p.resp + (size_t)rq.d.row * N, rq.d, rq.isb, N, tid, nthr);
   float2* Z = mini_fft<+1>(Y, X, p, tid, nthr);
   float2* __restrict__ o = p.out + (size_t)blockIdx.x * p.olen;
-  const int drop = P - p.olen;
+  const int drop = N - p.olen;
   for (int i = tid; i < p.olen; i += nthr) o[i] = Z[drop + i];
+}
+
+// ------------------------------------------------------------------------------
+// filter2 resident on the device: a bank's channels each run their private second filter (src/radio.c:1503-1513, created at
+// :1572-1594) between the channel kernel's rotated output and the demodulator, in block order on the demodulator stream.  One
+// workgroup per channel; the arithmetic is mini_ovs's (mini_fft, mini_gather with shift 0), what is new is that the overlap
+// lives here: one window of N = L + M - 1 samples per channel in HBM, [0, M-1) the history, behind it the blocks of the
+// running cycle.  With blocking B the filter takes L = B olen samples at a time: block j is number f2_phase(j) of its cycle
+// and FIRES when that is B - 1 -- every other block is PENDING, the reference's `continue` (:1509-1510): its olen samples
+// join the window, bb_power repeats the last firing block's value, and for a channel with a demodulator the n0 smoother in
+// front of that `continue` (:1468-1474) still takes its step; the slot is flagged CHZ_FLAG_PENDING, frame 2.
+// A firing block builds the window in LDS (what the window holds + the slot's olen newest samples), stores its last M-1
+// samples as the next history (every HBM read of the window is behind a barrier by then: the update is in place),
+// transforms, gathers, transforms back and leaves the last L samples and their mean |y|^2 (float products, double sum, :1516-1520).
+// ------------------------------------------------------------------------------
+#define CHZ_FLAG_PENDING_BIT 16
+__host__ __device__ inline int f2_phase(unsigned job, unsigned job0, int blocking) { return (int)((job - job0) % (unsigned)blocking); }
+struct F2Params {
+  const float2* in;          // [cap][olen] this slot's channel outputs (after fine tuning)
+  float2* win;               // [cap][N]
+  float2* out;               // [cap][L] this slot's filter2 output image (firing blocks only)
+  const float2* resp;        // [cap][N] as set_filter leaves them
+  const unsigned char* isb;  // [cap]
+  double* power;             // [cap] this slot's bb_power
+  double* last_power;        // [cap] bb_power of the last firing block
+  const double* n0;          // [cap] this slot's noise estimates (pending blocks of demodulated channels), or nullptr
+  const DemodChan* chan;     // [cap] or nullptr: the bank has no demodulators
+  DemodState* state;         // [cap]
+  DemodStatus* status;       // [cap] this slot
+  unsigned char* flags;      // [cap] this slot
+  double power_alpha;
+  ChanDesc d;                // the gather of shift 0 between two N-point transforms
+  MiniParams m;              // tw, N, stages
+  int olen, L, blocking;
+  unsigned job, job0;
+};
+__global__ void __launch_bounds__(256) f2_ovs(F2Params p) {
+  HIP_DYNAMIC_SHARED(float2, lds)
+  const int tid = threadIdx.x, nthr = blockDim.x, ch = blockIdx.x;
+  const int N = p.m.N, L = p.L, H = N - L;                  // H = M - 1 samples of history
+  double* red = reinterpret_cast<double*>(lds + 2 * N);     // one partial sum per wavefront, behind the two buffers
+  const int k = f2_phase(p.job, p.job0, p.blocking);
+  const float2* __restrict__ x = p.in + (size_t)ch * p.olen;
+  float2* w = p.win + (size_t)ch * N;
+  const int held = H + k * p.olen;                          // samples the window holds in front of this block's
+  if (k != p.blocking - 1) {
+    for (int i = tid; i < p.olen; i += nthr) w[held + i] = x[i];
+    if (tid == 0) {
+      p.power[ch] = p.last_power[ch];
+      if (p.chan != nullptr && p.chan[ch].on) {
+        DemodState* st = p.state + ch;
+        const double est = p.n0[ch];                        // src/radio.c:1466-1473
+        double n0 = st->n0;
+        if (n0 != n0) n0 = est;
+        else { const double diff = est - n0; n0 += p.power_alpha * diff; }
+        st->n0 = n0;
+        DemodStatus r = p.status[ch];                       // the other members keep what the slot's last frame left
+        r.frame = 2; r.n0 = n0;
+        p.status[ch] = r;
+        p.flags[ch] = (unsigned char)CHZ_FLAG_PENDING_BIT;
+      }
+    }
+    return;
+  }
+  float2* A = lds;
+  float2* B = lds + N;
+  for (int i = tid; i < N; i += nthr) A[i] = i < held ? w[i] : x[i - held];
+  __syncthreads();
+  for (int i = tid; i < H; i += nthr) w[i] = A[L + i];
+  float2* X = mini_fft<-1>(A, B, p.m, tid, nthr);
+  float2* Y = (X == A) ? B : A;
+  mini_gather(X, Y, p.resp + (size_t)ch * N, p.d, p.isb[ch] != 0, N, tid, nthr);
+  float2* Z = mini_fft<+1>(Y, X, p.m, tid, nthr);
+  float2* __restrict__ o = p.out + (size_t)ch * L;
+  double part = 0.0;
+  for (int i = tid; i < L; i += nthr) {
+    const float2 v = Z[H + i];
+    o[i] = v;
+    part += (double)(v.x * v.x + v.y * v.y);
+  }
+  part = wave_sum_f64(part);
+  if ((tid & 63) == 0) red[tid >> 6] = part;
+  __syncthreads();
+  if (tid == 0) {
+    double e = 0.0;
+    for (int wv = 0; wv < (nthr + 63) / 64; wv++) e += red[wv];
+    e /= L;
+    p.power[ch] = e; p.last_power[ch] = e;
+  }
 }
 
 // ------------------------------------------------------------------------------

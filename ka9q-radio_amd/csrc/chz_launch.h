@@ -266,6 +266,15 @@ inline int launch_demod(hipStream_t s, const DemodParams& p_in, hipEvent_t e0 = 
   }
   return 0;
 }
+// filter2 on the device (f2_ovs): one workgroup per channel, two N-point buffers in LDS and four doubles for the power sum; threads as mini_ovs's launch
+inline size_t f2_lds_bytes(int N) { return sizeof(float2) * 2 * (size_t)N + 4 * sizeof(double); }
+inline int f2_prepare(int N) { return f2_lds_bytes(N) > 64 * 1024 ? big_lds_prepare(reinterpret_cast<const void*>(f2_ovs)) : 0; }
+inline void launch_f2(hipStream_t s, const F2Params& p, int nch, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
+  if (nch <= 0) return;
+  const int N = p.m.N;
+  const int threads = N / 4 >= 256 ? 256 : (N / 4 >= 64 ? (N / 4 + 63) / 64 * 64 : 64);
+  CHZ_LAUNCH(f2_ovs, nch, threads, f2_lds_bytes(N), s, e0, e1, p);
+}
 // host side of the coherent modes and the PL-tone squelch: what init_pll() (src/osc.c:130-136, called once when the demodulator
 // starts, src/linear.c:41) and the tone set-up of demod_fm() (src/fm.c:50-61) leave behind
 inline DemodExt demod_ext_init() {

@@ -37,9 +37,9 @@ void chz_mini_destroy(chz_mini* m) {
 int chz_mini_create(chz_mini** out, int L, int M, int capacity, int device) {
   if (!out) return fail(-1, "null out pointer");
   *out = nullptr;
-  if (L < 1 || M < 1 || capacity < 1) return fail(-1, "bad mini-master geometry");
+  if (capacity < 1) return fail(-1, "bad mini-master geometry");
+  { char why[200]; const int rc = mini_check_geom(L, M, why, sizeof why); if (rc) return fail(rc, "%s", why); }
   const int N = L + M - 1;
-  if (N < 8 || N > 8192) return fail(-3, "mini masters cover 8 <= N <= 8192 (got %d); larger masters are engines", N);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(-2, "no HIP device: there is no CPU fallback");
   if (device < 0 || device >= ndev) return fail(-2, "device %d out of range (%d devices)", device, ndev);
@@ -47,7 +47,7 @@ int chz_mini_create(chz_mini** out, int L, int M, int capacity, int device) {
   chz_mini* m = new chz_mini();
   struct Guard { chz_mini* m; ~Guard() { if (m) chz_mini_destroy(m); } } guard{m};
   m->L = L; m->M = M; m->N = N; m->cap = capacity; m->device = device;
-  if (!mini_factor(N, m->radix, &m->nstages)) return fail(-3, "N=%d has a prime factor above 13: no mini-master transform", N);
+  (void)mini_factor(N, m->radix, &m->nstages);
   // two N-point buffers in LDS: beyond 4096 points that is more than the 64 KB a kernel gets without asking
   if (sizeof(float2) * 2 * (size_t)N > 64 * 1024 && big_lds_prepare(reinterpret_cast<const void*>(mini_ovs)))
     return fail(-3, "the runtime refuses %zu bytes of LDS per workgroup (N=%d)", sizeof(float2) * 2 * (size_t)N, N);

@@ -436,6 +436,28 @@ inline bool mini_factor(int N, int* radix, int* nstages) {
 }
 
 
+// the limits of a COMPLEX mini master of N = L + M - 1 points, refused at chz_mini_create and chz_bank_set_filter2 and nowhere else
+inline int mini_check_geom(int L, int M, char* why, size_t why_len) {
+  int rdx[CHZ_MINI_MAX_STAGES], nst = 0;
+  if (L < 1 || M < 1) { snprintf(why, why_len, "bad mini-master geometry"); return -1; }
+  const long long N = (long long)L + M - 1;
+  if (N < 8 || N > 8192) { snprintf(why, why_len, "mini masters cover 8 <= N <= 8192 (got %lld); larger masters are engines", N); return -3; }
+  if (!mini_factor((int)N, rdx, &nst)) { snprintf(why, why_len, "N=%lld has a prime factor above 13: no mini-master transform", N); return -3; }
+  return 0;
+}
+// ---- filter2 resident in a bank (f2_ovs): blocking B >= 1 as chan->filter2.blocking, L2 = B olen, M2 = 0 for radiod's own choice
+// round2(2 L2) - L2 + 1 (src/radio.c:1578-1579), N2 = L2 + M2 - 1 within mini_check_geom's limits.  out3: L2, M2, N2
+inline int f2_check_geom(int olen, int blocking, int M2, int out3[3], char* why, size_t why_len) {
+  if (olen < 1 || blocking < 1 || M2 < 0) { snprintf(why, why_len, "bad filter2 geometry (olen %d, blocking %d, M2 %d)", olen, blocking, M2); return -1; }
+  const long long L2 = (long long)olen * blocking;
+  if (L2 > 8192) { snprintf(why, why_len, "filter2 of %d blocks of %d samples: mini masters cover 8 <= N <= 8192", blocking, olen); return -3; }
+  if (M2 == 0) { long long r = 1; while (r < 2 * L2) r <<= 1; M2 = (int)(r - L2 + 1); }       // round2(): the next power of two (src/misc.c)
+  const int rc = mini_check_geom((int)L2, M2, why, why_len);
+  if (rc) return rc;
+  if (out3) { out3[0] = (int)L2; out3[1] = M2; out3[2] = (int)L2 + M2 - 1; }
+  return 0;
+}
+
 // ---- pooled small REAL masters (rmini_ovs): what a master of N points with slaves of P_s points asks of a workgroup -------------
 // LDS: two N/2-point buffers for the forward transform, then the N/2 + 1 bins plus two buffers of the largest slave.  Threads: N/8
 // rounded up to whole wavefronts, at most 256 while four workgroups share a CU (<= 40 KB of LDS), at most 1024 beyond (see rmini_ovs).

@@ -58,6 +58,8 @@ class WfmStatus(C.Structure):
 
 
 PCM_S16BE, PCM_S16LE, PCM_F32LE, PCM_F32BE, PCM_MULAW, PCM_ALAW, PCM_F16LE, PCM_F16BE = 0, 1, 2, 3, 4, 5, 6, 7
+FLAG_NO_SAMPLES, FLAG_MUTE, FLAG_PLL_LOCK, FLAG_TONE_MUTE, FLAG_PENDING = 1, 2, 4, 8, 16
+FRAME_PENDING = 2        # DemodStatus.frame of a filter2 bank's pending block
 
 
 # every symbol include/chz_engine.h declares (checked by tests/test_host_logic.py and __graft_entry__.build())
@@ -82,6 +84,8 @@ SYMBOLS = [
     "chz_comm_barrier", "chz_comm_allreduce_max", "chz_spectrum_broadcast", "chz_spectrum_exchange_rows", "chz_run_blocks_sharded",
     "chz_comm_create_local", "chz_spectrum_broadcast_local", "chz_set_option",
     "chz_welch_create", "chz_welch_destroy", "chz_welch_set_window", "chz_welch_configure", "chz_welch_poll", "chz_welch_read", "chz_welch_read_async",
+    "chz_bank_filter2_check", "chz_bank_set_filter2", "chz_bank_filter2_geometry", "chz_bank_set_filter2_responses", "chz_bank_set_filter2_isb",
+    "chz_bank_filter2_reset", "chz_bank_filter2_read", "chz_bank_filter2_read_async",
     "chz_bank_welch_create", "chz_bank_welch_attach", "chz_bank_welch_detach", "chz_bank_welch_configure", "chz_bank_welch_poll", "chz_bank_welch_steps",
 ]
 
@@ -209,6 +213,14 @@ def lib():
         L.chz_welch_poll.argtypes = [_vp, _i, _i, _vp, C.c_longlong]
         L.chz_welch_read.argtypes = [_vp, _i, _i, _i, _vp, _vp]
         L.chz_welch_read_async.argtypes = [_vp, _i, _i, _i, _vp, _vp]
+        L.chz_bank_filter2_check.argtypes = [_i, _i, _i]
+        L.chz_bank_set_filter2.argtypes = [_vp, _i, _u, _i, _i]
+        L.chz_bank_filter2_geometry.argtypes = [_vp, _i, C.POINTER(_i * 3)]
+        L.chz_bank_set_filter2_responses.argtypes = [_vp, _i, _i, _i, _vp]
+        L.chz_bank_set_filter2_isb.argtypes = [_vp, _i, _i, _i, _vp]
+        L.chz_bank_filter2_reset.argtypes = [_vp, _i, _u, _i, _i]
+        L.chz_bank_filter2_read.argtypes = [_vp, _i, _i, _i, _i, _vp]
+        L.chz_bank_filter2_read_async.argtypes = [_vp, _i, _i, _i, _i, _vp]
         L.chz_bank_welch_create.argtypes = [_vp, _i, _i, _i, _i, _i]
         L.chz_bank_welch_attach.argtypes = [_vp, _i, _i, _i, _u]
         L.chz_bank_welch_detach.argtypes = [_vp, _i, _i]
@@ -545,6 +557,46 @@ class Bank:
         out = np.zeros((n, self.olen), self._dtype)
         _check(lib().chz_bank_read_async(self.eng._h, self.id, slot, ch0, n, out.ctypes.data))
         self.eng.sync()
+        return out
+
+    # ---- filter2 resident on the device (chz_bank_set_filter2 & co., include/chz_engine.h)
+    @staticmethod
+    def filter2_check(olen, blocking, M2=0):
+        """Would set_filter2 take this geometry?  Raises ChzError with the reason if not; touches no device."""
+        _check(lib().chz_bank_filter2_check(int(olen), int(blocking), int(M2)))
+
+    def set_filter2(self, job0, blocking, M2=0):
+        """The channels' private second filter (src/radio.c:1503-1513) as a stage of the block pipeline: cycles of `blocking` blocks
+        from block job0 on, M2 = 0 for radiod's own impulse length.  Returns (L2, M2, N2)."""
+        _check(lib().chz_bank_set_filter2(self.eng._h, self.id, job0 & 0xFFFFFFFF, int(blocking), int(M2)))
+        return self.filter2_geometry()
+
+    def filter2_geometry(self):
+        out = (_i * 3)()
+        _check(lib().chz_bank_filter2_geometry(self.eng._h, self.id, C.byref(out)))
+        return tuple(out)
+
+    def set_filter2_responses(self, ch0, resp):
+        """complex64[n][N2] as set_filter leaves them; in stream order from the next block enqueued."""
+        r = np.ascontiguousarray(resp, np.complex64).reshape(-1, self.filter2_geometry()[2])
+        _check(lib().chz_bank_set_filter2_responses(self.eng._h, self.id, ch0, r.shape[0], r.ctypes.data))
+
+    def set_filter2_isb(self, ch0, flags):
+        f = np.ascontiguousarray(flags, np.uint8).reshape(-1)
+        _check(lib().chz_bank_set_filter2_isb(self.eng._h, self.id, ch0, f.shape[0], f.ctypes.data))
+
+    def filter2_reset(self, job, ch0=0, n=None):
+        """Zero the windows of channels [ch0, ch0+n) from block `job` on: the next block, and the first of a cycle."""
+        if n is None:
+            n = self.active - ch0
+        _check(lib().chz_bank_filter2_reset(self.eng._h, self.id, job & 0xFFFFFFFF, ch0, n))
+
+    def read_filter2(self, slot, ch0=0, n=None):
+        """complex64[n][L2]: filter2's output of the block that fired on `slot` (ChzError if the slot's last block was pending)."""
+        if n is None:
+            n = self.active - ch0
+        out = np.zeros((n, self.filter2_geometry()[0]), np.complex64)
+        _check(lib().chz_bank_filter2_read(self.eng._h, self.id, slot, ch0, n, out.ctypes.data))
         return out
 
     def output_ptr(self, slot=0):
