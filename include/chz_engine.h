@@ -510,6 +510,54 @@ int chz_wfm_set_response(chz_wfm *m, int inst, int slave, const float *resp);   
 int chz_wfm_execute(chz_wfm *m, int n, const int *inst, const float *const *bb, int bb_on_device, const double *bb_power, const double *n0,
                     void *const *pcm, chz_wfm_status *status);
 
+/* ---- Pooled AFSK / AX.25 packet decoders: packetd's decode_task() (src/packetd.c:485-629, hdlc_process() :634-682, crc_good()
+ * src/ax25.c:139-155) from a session's 16-bit audio to its frames ------
+ * A pool is one geometry: (L, M, samprate, bitrate, mark, space, input byte order); packetd's own is L 960, M 961, bitrate 1200, mark 1200,
+ * space 2200 at the stream's sample rate, samppbit = (int)(samprate / bitrate).  One launch serves every session that is due, one
+ * workgroup per request: the L samples are converted (:551-552) and appended to the session's M - 1 old ones, the REAL master and its one
+ * COMPLEX slave (olen L, shift 0; chz_rmini_*'s transform and gather rules, the response from the host) make them analytic, and one lane
+ * walks the block as the reference does: two tone oscillators (src/osc.c, renormalised every 16384 steps), on-time and offset
+ * integrators, the Gardner clock, NRZI, HDLC and the CRC, all in double.  The decoder is a recurrence over blocks: the filter's history,
+ * oscillators, integrators, symphase / last_val / mid_val and the HDLC state with its 16384-byte frame buffer live on the device, per
+ * instance, all zero after chz_afsk_add.  What stays with the caller: RTP, the reference's input feeder (five blocks of zeros after a
+ * block that ends in 100 zero samples, :540-546) and whatever parses the frames (APRS).
+ * Limits, refused at chz_afsk_create / chz_afsk_check and nowhere else: what chz_rmini_create refuses for that master and slave;
+ * samppbit < 4; a tone at or above samprate / 2; a block that can hold more than 64 decisions, ceil(L / (samppbit - 1)) > 64 (they are
+ * reported as one 64-bit word).  A frame and its closing flag take at least 32 decisions, so at most CHZ_AFSK_STATUS_FRAMES = 64 / 32 = 2
+ * frames complete in one block. */
+#define CHZ_AFSK_BE 0                 /* samples as RTP carries them (ntohs at :551) */
+#define CHZ_AFSK_LE 1
+#define CHZ_AFSK_STATUS_FRAMES 2
+#define CHZ_AFSK_FRAME_MAX 16384      /* sizeof(hdlc.frame): no frame is longer */
+typedef struct chz_afsk chz_afsk;
+typedef struct chz_afsk_status {
+  int ndecisions;               /* bit decisions taken in this block */
+  int symphase;                 /* at the end of the block */
+  unsigned long long bits;      /* decision i in bit i: 1 = no transition (an NRZI one) */
+  double last_val, mid_val;     /* at the end of the block */
+  int flag_seen, frame_bits;    /* hdlc state at the end of the block */
+  int crc_failures;             /* frames of this block whose CRC failed: counted, not delivered */
+  int nframes;                  /* frames completed in this block, 0 .. CHZ_AFSK_STATUS_FRAMES */
+  int frame_len[CHZ_AFSK_STATUS_FRAMES];   /* their lengths in bytes, the two CRC bytes included */
+} chz_afsk_status;
+int chz_afsk_check(int L, int M, double samprate, double bitrate, double mark, double space, int byte_order);   /* would chz_afsk_create take this? 0, or < 0 and chz_last_error(); touches no device */
+int chz_afsk_create(chz_afsk **out, int L, int M, double samprate, double bitrate, double mark, double space, int byte_order, int capacity, int device);
+void chz_afsk_destroy(chz_afsk *m);
+int chz_afsk_capacity(const chz_afsk *m);
+int chz_afsk_geometry(const chz_afsk *m, int out4[4]);                          /* L, M, N, samppbit */
+int chz_afsk_add(chz_afsk *m);                                                  /* -> instance index; all state zero, as a fresh decode_task */
+int chz_afsk_release(chz_afsk *m, int inst);
+int chz_afsk_set_response(chz_afsk *m, int inst, const float *resp);            /* N complex, as chz_rmini_set_response (packetd: set_filter(900 / samprate, 2500 / samprate, 3.0)) */
+/* One block of n decoders, one H2D, ONE launch and one D2H of status records per chunk of `capacity`: instance inst[i] (at most once in
+ * a call) takes the L 16-bit samples at samples[i] in the pool's byte order -- host memory (samples_on_device = 0), or device memory that
+ * is complete before the call (1; read in place, 2-byte aligned).  Frame j < status[i].nframes lands at frames[i] + j * frame_stride, at
+ * most frame_stride bytes of its status[i].frame_len[j]; the rest of frames[i] stays untouched.  Only the bytes of frames that completed
+ * cross the link, in a second copy sized by their lengths (one per request that completed a frame, one wait); a block without a frame
+ * returns status only.  Every request is checked before the first launch: a refused call has written nothing and advanced no state.
+ * Synchronous, thread-safe. */
+int chz_afsk_execute(chz_afsk *m, int n, const int *inst, const void *const *samples, int samples_on_device, chz_afsk_status *status,
+                     unsigned char *const *frames, int frame_stride);
+
 /* ---- Welch power spectra of the raw input: radiod's wideband spectrum analyser (wideband_poll(), src/spectrum.c:308-522) on the
  * samples the engine's input ring holds (float REAL, float COMPLEX or the int16 of chz_input_write_i16).  A bank holds `capacity`
  * analysers sharing one fft_n (= lrint(samprate / rbw): any length from 8 to 2^20 points; one with a prime factor above 13 runs as

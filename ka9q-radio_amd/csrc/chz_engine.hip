@@ -2281,4 +2281,5 @@ int chz_run_blocks(chz_engine* e, unsigned job0, int nblocks, int mode, int inst
 #include "chz_filter2.inc"
 #include "chz_rmini.inc"
 #include "chz_wfm.inc"
+#include "chz_afsk.inc"
 #include "chz_welch.inc"

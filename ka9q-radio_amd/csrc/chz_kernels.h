@@ -3852,6 +3852,167 @@ __global__ void __launch_bounds__(1024) wfm_ovs(WfmParams p) {
 }
 
 // ------------------------------------------------------------------------------
+// packetd's decode_task() (src/packetd.c:485-629) with hdlc_process() (:634-682) and crc_good() (src/ax25.c:139-155): the AFSK / AX.25
+// packet decoder between a session's 16-bit audio and its frames.  One workgroup per request.  The workgroup converts the block's L
+// samples (:551-552), puts them behind the session's M - 1 old ones (HBM, like wfm_ovs's composite history) and runs rmini_ovs's
+// forward transform, split and ONE COMPLEX slave (olen = L, P = N, shift 0): the analytic signal lands in LDS.  Everything behind the
+// filter is a recurrence in double whose run boundaries depend on earlier decisions (the Gardner step moves symphase by +-1), so ONE
+// lane walks the L samples in the reference's own order: the two tone oscillators (src/osc.c:28-70: phasor *= step, renormalised
+// every 16384 steps), the on-time and offset integrators, the decisions, NRZI, HDLC and the CRC.  A completed frame is copied out of
+// the session's frame buffer into the request's output area at once (the next frame starts accumulating within the same block); the
+// second frame of a block lands behind the first, 8-byte aligned.
+// LDS: rmini_ovs's, 8 * max(N, N/2 + 1 + 2 N) bytes (packetd: 38,408 B).
+// ------------------------------------------------------------------------------
+#define CHZ_AFSK_FRAME_BYTES 16384             // sizeof(hdlc.frame), src/packetd.c:29
+#define CHZ_AFSK_FRAME_PITCH (CHZ_AFSK_FRAME_BYTES + 8)   // :667 tests with >, so bit 131072 is still written: one byte beyond the reference's array
+#define CHZ_AFSK_OUT_PITCH (CHZ_AFSK_FRAME_BYTES + 16)    // a request's output area: the longest frame, 8-byte aligned, and a second one of at most 7 bytes
+#define CHZ_AFSK_MAX_FRAMES 2                  // 64 decisions a block, a frame and its flag take at least 32
+#define CHZ_AFSK_RENORM 16384                  // Renorm_rate, src/osc.c:16
+struct AfskState {
+  double mark_ph[2], space_ph[2];              // the oscillators' phasors
+  double mark_acc[2], space_acc[2], mark_off[2], space_off[2];
+  double last_val, mid_val;
+  int mark_steps, space_steps, symphase, init;
+  int last_bits, flag_seen, frame_bits, cur_byte;
+};
+struct AfskReq { const unsigned short* samples; int inst, pad; };   // L 16-bit samples (device), any 2-byte alignment
+struct AfskStatusK { int ndecisions, symphase; unsigned long long bits; double last_val, mid_val; int flag_seen, frame_bits, crc_failures, nframes, frame_len[CHZ_AFSK_MAX_FRAMES]; };
+struct AfskParams {
+  const AfskReq* req;     // [nreq]
+  AfskState* state;       // [ninst]
+  float* hist;            // [ninst][M - 1]
+  unsigned char* frame;   // [ninst][CHZ_AFSK_FRAME_PITCH]
+  unsigned char* out;     // [nreq][CHZ_AFSK_OUT_PITCH]
+  AfskStatusK* status;    // [nreq]
+  const float2* tw_split; // [N/2 + 1] e^{-2 pi i k / N}
+  MiniParams fwd;         // the N/2-point forward transform
+  RminiSlave sl;          // the COMPLEX slave: m.N = N, m.olen = L, m.resp = [ninst][N]
+  ChanDesc d;             // its gather (row: the instance, filled in per request)
+  int N, L, samppbit, big_endian;
+  double twist;           // mark / space (:486)
+  double mark_step[2], space_step[2];          // cispi(-2 tone / samprate) (:503,507)
+};
+
+__device__ __forceinline__ bool afsk_crc_good(const unsigned char* f, int length) {      // src/ax25.c:139-155
+  unsigned crc = 0xffff;
+  for (int k = 0; k < length; k++) {
+    unsigned byte = f[k];
+    for (int i = 0; i < 8; i++) {
+      const unsigned feedback = ((crc ^ byte) & 1) ? 0x8408u : 0u;
+      crc = (crc >> 1) ^ feedback;
+      byte >>= 1;
+    }
+  }
+  return crc == 0xf0b8;
+}
+// hdlc_process(): > 0 the bytes of a complete valid frame (frame_bits already 0, as the caller leaves it at :617), -1 a CRC failure
+__device__ __forceinline__ int afsk_hdlc(AfskState& st, unsigned char* __restrict__ frame, int bit) {
+  st.last_bits = ((st.last_bits << 1) | (bit & 1)) & 0xff;                 // (only the low eight bits are ever looked at)
+  if (st.last_bits == 0x7e) {
+    const int bytes = (st.frame_bits - 7) >> 3;
+    st.frame_bits = 0;
+    if (st.flag_seen && bytes > 2) return afsk_crc_good(frame, bytes) ? bytes : -1;
+    st.flag_seen = 1;
+    return 0;
+  }
+  if (!st.flag_seen) return 0;
+  if ((st.last_bits & 0x7f) == 0x7f) { st.frame_bits = 0; st.flag_seen = 0; return 0; }      // seven ones: abort
+  if ((st.last_bits & 0x3f) == 0x3e) return 0;                             // a stuffed zero
+  if (st.frame_bits > (CHZ_AFSK_FRAME_BYTES << 3)) { st.frame_bits = 0; st.flag_seen = 0; return 0; }      // too long: abort
+  if ((st.frame_bits & 7) == 0) st.cur_byte = 0;                           // the byte being filled travels in the state: a store per bit, no load
+  st.cur_byte |= (bit & 1) << (st.frame_bits & 7);
+  frame[st.frame_bits >> 3] = (unsigned char)st.cur_byte;
+  st.frame_bits++;
+  return 0;
+}
+__device__ __forceinline__ void afsk_step_osc(double* ph, int& steps, const double* step, double& re, double& im) {      // step_osc(), rate = 0
+  if (--steps <= 0) {
+    steps = CHZ_AFSK_RENORM;
+    const double a = hypot(ph[0], ph[1]);
+    ph[0] /= a; ph[1] /= a;
+  }
+  re = ph[0]; im = ph[1];
+  ph[0] = re * step[0] - im * step[1];
+  ph[1] = re * step[1] + im * step[0];
+}
+
+__global__ void __launch_bounds__(1024) afsk_ovs(AfskParams p) {
+  HIP_DYNAMIC_SHARED(float2, lds)
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int N = p.N, H = N / 2, L = p.L, Mm1 = N - L;
+  const AfskReq rq = p.req[blockIdx.x];
+  // ---- the window: M - 1 old samples, then the block's L (:551-552: host order, scaled by 2^-15 -- exact in a float)
+  float* Af = reinterpret_cast<float*>(lds);
+  float* __restrict__ hist = p.hist + (size_t)rq.inst * Mm1;
+  for (int n = tid; n < Mm1; n += nthr) Af[n] = hist[n];
+  for (int n = tid; n < L; n += nthr) {
+    unsigned v = rq.samples[n];
+    if (p.big_endian) v = ((v & 0xffu) << 8) | (v >> 8);
+    Af[Mm1 + n] = (float)(short)v * (1.0f / 32768.0f);
+  }
+  __syncthreads();
+  for (int n = tid; n < Mm1; n += nthr) hist[n] = Af[L + n];               // the window's last M - 1 samples are the next block's old ones
+  __syncthreads();
+  // ---- the filter (:553-555): rmini_ovs's forward transform, split and slave
+  float2* A = lds;
+  float2* B = lds + H;
+  const float2* Z = mini_fft<-1>(A, B, p.fwd, tid, nthr);
+  float2* S = lds;
+  rmini_split(Z, S, p.tw_split, H, tid, nthr);
+  float2* Y = lds + H + 1;
+  const int no_isb = 0;
+  ChanDesc d = p.d; d.row = rq.inst;
+  const float2* T = rmini_slave(S, Y, p.sl, d, no_isb, H + 1, tid, nthr) + Mm1;      // the last L of the N samples
+  if (tid != 0) return;                                                    // (no barrier follows)
+  // ---- correlators, clock, NRZI and HDLC (:556-625), one lane in the reference's order
+  AfskState st = p.state[rq.inst];
+  if (!st.init) {                                                          // a fresh decode_task: set_osc() on a zeroed struct osc
+    st.mark_ph[0] = st.space_ph[0] = 1.0; st.mark_steps = st.space_steps = CHZ_AFSK_RENORM; st.init = 1;
+  }
+  unsigned char* __restrict__ frame = p.frame + (size_t)rq.inst * CHZ_AFSK_FRAME_PITCH;
+  unsigned char* __restrict__ out = p.out + (size_t)blockIdx.x * CHZ_AFSK_OUT_PITCH;
+  AfskStatusK so{};
+  int out_at = 0;
+  const int sps = p.samppbit, half = sps / 2;
+  for (int n = 0; n < L; n++) {
+    const double xr = (double)T[n].x, xi = (double)T[n].y;
+    double cr, ci;
+    afsk_step_osc(st.mark_ph, st.mark_steps, p.mark_step, cr, ci);
+    double sr = xr * cr - xi * ci, si = xr * ci + xi * cr;
+    st.mark_acc[0] += sr; st.mark_acc[1] += si; st.mark_off[0] += sr; st.mark_off[1] += si;
+    afsk_step_osc(st.space_ph, st.space_steps, p.space_step, cr, ci);
+    sr = xr * cr - xi * ci; si = xr * ci + xi * cr;
+    st.space_acc[0] += sr; st.space_acc[1] += si; st.space_off[0] += sr; st.space_off[1] += si;
+    if (++st.symphase == half) {
+      st.mid_val = (st.mark_off[0] * st.mark_off[0] + st.mark_off[1] * st.mark_off[1]) - p.twist * (st.space_off[0] * st.space_off[0] + st.space_off[1] * st.space_off[1]);
+      st.mark_off[0] = st.mark_off[1] = st.space_off[0] = st.space_off[1] = 0.0;
+    }
+    if (st.symphase < sps) continue;
+    const double cur = (st.mark_acc[0] * st.mark_acc[0] + st.mark_acc[1] * st.mark_acc[1]) - p.twist * (st.space_acc[0] * st.space_acc[0] + st.space_acc[1] * st.space_acc[1]);
+    st.mark_acc[0] = st.mark_acc[1] = st.space_acc[0] = st.space_acc[1] = 0.0;
+    if (cur * st.last_val >= 0) {                                          // no transition: an NRZI one
+      st.symphase = 0;
+      if (so.ndecisions < 64) so.bits |= 1ull << so.ndecisions;
+      (void)afsk_hdlc(st, frame, 1);
+    } else {
+      st.symphase = ((cur - st.last_val) * st.mid_val) > 0 ? +1 : -1;
+      const int bytes = afsk_hdlc(st, frame, 0);
+      if (bytes < 0) so.crc_failures++;
+      else if (bytes > 0 && so.nframes < CHZ_AFSK_MAX_FRAMES && out_at + bytes <= CHZ_AFSK_OUT_PITCH) {      // (chz_afsk_check's 64-decision bound keeps both true)
+        for (int k = 0; k < bytes; k++) out[out_at + k] = frame[k];
+        so.frame_len[so.nframes++] = bytes;
+        out_at += (bytes + 7) & ~7;
+      }
+    }
+    so.ndecisions++;
+    st.last_val = cur;
+  }
+  so.symphase = st.symphase; so.last_val = st.last_val; so.mid_val = st.mid_val; so.flag_seen = st.flag_seen; so.frame_bits = st.frame_bits;
+  p.state[rq.inst] = st;
+  p.status[blockIdx.x] = so;
+}
+
+// ------------------------------------------------------------------------------
 // K3+K4 for ANY P without a prime factor above 13 -- the sizes the register-tiled chan_ifft / chan_c2r menu does not hold
 // (wfm's 384 kHz channel on a 20 ms block with overlap 5 is P = 9600, src/wfm.c:37-39; odd sample rates).  One workgroup
 // per channel: the gather x response of src/filter.c:728-911 lands in LDS in FFT order (COMPLEX or REAL output, ISB

@@ -538,4 +538,25 @@ inline void wfm_launch_geom(int N, int P, int olen, int* out_off, int* red_off, 
   *threads = q < 64 ? 64 : (q > top ? top : q);
 }
 
+// ---- pooled AFSK / AX.25 packet decoders (afsk_ovs): packetd's decode_task() for (L, M, samprate, bitrate, mark, space) ------------------
+// out4: L, M, N, samppbit = (int)(samprate / bitrate) (src/packetd.c:509).  Refuses what rmini_check_geom refuses for the REAL master
+// (L, M) with its one COMPLEX slave of olen L, fewer than 4 samples a bit (samppbit / 2 and samppbit - 1 must both be clock phases of their
+// own), a tone at or above samprate / 2, and a block that can hold more than 64 decisions: after a transition the clock may restart at
+// +1, so two decisions lie at least samppbit - 1 samples apart, and a block's decisions travel as one 64-bit word.
+#define CHZ_AFSK_MAX_DECISIONS 64
+inline int afsk_check_geom(int L, int M, double samprate, double bitrate, double mark, double space, int out4[4], char* why, size_t why_len) {
+  if (!(samprate > 0) || !(bitrate > 0) || !(mark > 0) || !(space > 0) || !(samprate < 1e9)) { snprintf(why, why_len, "bad AFSK rates (samprate %g, bitrate %g, mark %g, space %g)", samprate, bitrate, mark, space); return -1; }
+  const int olen[1] = {L}, type[1] = {CHZ_IN_COMPLEX};
+  const int rc = rmini_check_geom(L, M, 1, olen, type, nullptr, why, why_len);
+  if (rc) return rc;
+  if (!(samprate / bitrate < 1e6)) { snprintf(why, why_len, "samprate / bitrate = %g samples a bit: bad AFSK rates", samprate / bitrate); return -1; }      // (the cast below stays defined)
+  const int samppbit = (int)(samprate / bitrate);
+  if (samppbit < 4) { snprintf(why, why_len, "samppbit = (int)(%g / %g) = %d: the bit clock needs at least 4 samples a bit", samprate, bitrate, samppbit); return -3; }
+  if (!(mark < samprate / 2) || !(space < samprate / 2)) { snprintf(why, why_len, "tones of %g and %g Hz do not lie below samprate / 2 = %g Hz", mark, space, samprate / 2); return -3; }
+  const int worst = (L + samppbit - 2) / (samppbit - 1);
+  if (worst > CHZ_AFSK_MAX_DECISIONS) { snprintf(why, why_len, "a block of %d samples at %d samples a bit can hold %d decisions, more than the 64 a status record reports", L, samppbit, worst); return -3; }
+  if (out4) { out4[0] = L; out4[1] = M; out4[2] = L + M - 1; out4[3] = samppbit; }
+  return 0;
+}
+
 }  // namespace chz

@@ -57,6 +57,14 @@ class WfmStatus(C.Structure):
                 ("snr", _d), ("foffset", _d), ("pdeviation", _d), ("output_power", _d), ("gain", _d), ("subc_amp", _d)]
 
 
+class AfskStatus(C.Structure):
+    """chz_afsk_status: one block of one packet decoder (bits: decision i in bit i, 1 = no transition)."""
+    _fields_ = [("ndecisions", _i), ("symphase", _i), ("bits", C.c_ulonglong), ("last_val", _d), ("mid_val", _d),
+                ("flag_seen", _i), ("frame_bits", _i), ("crc_failures", _i), ("nframes", _i), ("frame_len", _i * 2)]
+
+
+AFSK_BE, AFSK_LE = 0, 1
+AFSK_FRAME_MAX = 16384
 PCM_S16BE, PCM_S16LE, PCM_F32LE, PCM_F32BE, PCM_MULAW, PCM_ALAW, PCM_F16LE, PCM_F16BE = 0, 1, 2, 3, 4, 5, 6, 7
 FLAG_NO_SAMPLES, FLAG_MUTE, FLAG_PLL_LOCK, FLAG_TONE_MUTE, FLAG_PENDING = 1, 2, 4, 8, 16
 FRAME_PENDING = 2        # DemodStatus.frame of a filter2 bank's pending block
@@ -81,6 +89,8 @@ SYMBOLS = [
     "chz_rmini_create", "chz_rmini_destroy", "chz_rmini_check", "chz_rmini_capacity", "chz_rmini_add", "chz_rmini_release", "chz_rmini_set_response", "chz_rmini_execute",
     "chz_wfm_check", "chz_wfm_create", "chz_wfm_destroy", "chz_wfm_capacity", "chz_wfm_geometry", "chz_wfm_add", "chz_wfm_release", "chz_wfm_set_params",
     "chz_wfm_set_response", "chz_wfm_execute",
+    "chz_afsk_check", "chz_afsk_create", "chz_afsk_destroy", "chz_afsk_capacity", "chz_afsk_geometry", "chz_afsk_add", "chz_afsk_release",
+    "chz_afsk_set_response", "chz_afsk_execute",
     "chz_comm_barrier", "chz_comm_allreduce_max", "chz_spectrum_broadcast", "chz_spectrum_exchange_rows", "chz_run_blocks_sharded",
     "chz_comm_create_local", "chz_spectrum_broadcast_local", "chz_set_option",
     "chz_welch_create", "chz_welch_destroy", "chz_welch_set_window", "chz_welch_configure", "chz_welch_poll", "chz_welch_read", "chz_welch_read_async",
@@ -169,6 +179,15 @@ def lib():
         L.chz_wfm_set_params.argtypes = [_vp, _i, C.POINTER(WfmParams)]
         L.chz_wfm_set_response.argtypes = [_vp, _i, _i, _vp]
         L.chz_wfm_execute.argtypes = [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]
+        L.chz_afsk_check.argtypes = [_i, _i, _d, _d, _d, _d, _i]
+        L.chz_afsk_create.argtypes = [C.POINTER(_vp), _i, _i, _d, _d, _d, _d, _i, _i, _i]
+        L.chz_afsk_destroy.argtypes = [_vp]; L.chz_afsk_destroy.restype = None
+        L.chz_afsk_capacity.argtypes = [_vp]
+        L.chz_afsk_geometry.argtypes = [_vp, C.POINTER(_i * 4)]
+        L.chz_afsk_add.argtypes = [_vp]
+        L.chz_afsk_release.argtypes = [_vp, _i]
+        L.chz_afsk_set_response.argtypes = [_vp, _i, _vp]
+        L.chz_afsk_execute.argtypes = [_vp, _i, _vp, _vp, _i, _vp, _vp, _i]
         L.chz_comm_unique_id.argtypes = [_vp]
         L.chz_comm_create.argtypes = [C.POINTER(_vp), _i, _i, _vp, _i]
         L.chz_comm_create_file.argtypes = [C.POINTER(_vp), _i, _i, C.c_char_p, _i, _d]
@@ -914,6 +933,70 @@ class WfmPool:
     def close(self):
         if self._h:
             lib().chz_wfm_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AfskPool:
+    """Pool of AFSK / AX.25 packet decoders of one geometry (packetd's decode_task(), src/packetd.c): 16-bit audio in, a status record per
+    block and the frames that completed (CRC included) out.  RTP, the reference's zero-flush feeder and APRS parsing stay with the caller."""
+
+    def __init__(self, L, M, samprate, capacity, bitrate=1200.0, mark=1200.0, space=2200.0, byte_order=AFSK_BE, device=0, frame_stride=AFSK_FRAME_MAX):
+        self._h = _vp()
+        _check(lib().chz_afsk_create(C.byref(self._h), L, M, float(samprate), float(bitrate), float(mark), float(space), byte_order, capacity, device))
+        g = (_i * 4)()
+        _check(lib().chz_afsk_geometry(self._h, C.byref(g)))
+        self.geometry = dict(zip(("L", "M", "N", "samppbit"), (int(v) for v in g)))
+        self.L, self.M, self.N, self.samppbit = (self.geometry[k] for k in ("L", "M", "N", "samppbit"))
+        self.samprate, self.capacity, self.byte_order, self.frame_stride = float(samprate), capacity, byte_order, int(frame_stride)
+
+    @staticmethod
+    def check(L, M, samprate, bitrate=1200.0, mark=1200.0, space=2200.0, byte_order=AFSK_BE):
+        """Would a pool of this geometry be created?  Raises ChzError with the reason if not; touches no device."""
+        _check(lib().chz_afsk_check(L, M, float(samprate), float(bitrate), float(mark), float(space), byte_order))
+
+    def add(self):
+        return _check(lib().chz_afsk_add(self._h))
+
+    def release(self, inst):
+        _check(lib().chz_afsk_release(self._h, inst))
+
+    def set_response(self, inst, resp):
+        r = np.ascontiguousarray(resp, np.complex64).reshape(-1)
+        assert r.shape[0] == self.N
+        _check(lib().chz_afsk_set_response(self._h, inst, r.ctypes.data))
+
+    def execute(self, insts, samples, on_device=False, frames_buf=None, status_buf=None):
+        """samples: [n][L] 16-bit words in the pool's byte order as they lie in memory (an int16 / uint16 array or a list of n rows, of which
+        one may be None: a null row, which the call refuses), or (on_device) n device addresses of L such words each, complete before the call.
+        frames_buf, status_buf: the caller's own uint8 buffers [n][2 * frame_stride] and [n][sizeof(AfskStatus)] (a caller that runs every block
+        keeps them; without them each call makes its own).  -> (AfskStatus array, list of n lists of frames as bytes)."""
+        insts = np.ascontiguousarray(insts, np.int32)
+        n = insts.shape[0]
+        if on_device:
+            sp = (_vp * n)(*[int(a) if a else None for a in samples])
+        else:
+            rows = [None if r is None else np.ascontiguousarray(r).view(np.uint16).reshape(self.L) for r in samples]
+            sp = (_vp * n)(*[None if r is None else r.ctypes.data for r in rows])
+        raw = np.empty((n, 2 * self.frame_stride), np.uint8) if frames_buf is None else frames_buf
+        sraw = np.empty((n, C.sizeof(AfskStatus)), np.uint8) if status_buf is None else status_buf
+        assert raw.dtype == np.uint8 and raw.flags.c_contiguous and raw.shape == (n, 2 * self.frame_stride)
+        assert sraw.dtype == np.uint8 and sraw.flags.c_contiguous and sraw.shape == (n, C.sizeof(AfskStatus))
+        fp = (_vp * n)(*[raw[i].ctypes.data for i in range(n)])
+        _check(lib().chz_afsk_execute(self._h, n, insts.ctypes.data, sp, int(bool(on_device)), sraw.ctypes.data, fp, self.frame_stride))
+        status = (AfskStatus * n).from_buffer(sraw)
+        frames = [[raw[i, j * self.frame_stride:j * self.frame_stride + min(status[i].frame_len[j], self.frame_stride)].tobytes()
+                   for j in range(status[i].nframes)] for i in range(n)]
+        return status, frames
+
+    def close(self):
+        if self._h:
+            lib().chz_afsk_destroy(self._h)
             self._h = _vp()
 
     def __del__(self):
