@@ -558,6 +558,49 @@ int chz_afsk_set_response(chz_afsk *m, int inst, const float *resp);            
 int chz_afsk_execute(chz_afsk *m, int n, const int *inst, const void *const *samples, int samples_on_device, chz_afsk_status *status,
                      unsigned char *const *frames, int frame_stride);
 
+/* ---- Pooled CTCSS / PL tone decoders: ctcss's tone search (src/ctcss.c:268-309, process_pl() :392-419, the oscillators of src/osc.c:28-70)
+ * from a session's 16-bit audio to the index of the tone it carries ------
+ * A pool is one geometry: (samprate, input byte order, tone table).  The sample rate alone fixes the rest as ctcss does: blocks of
+ * L = lrint(0.2 samprate) samples, M = L + 1, N = 2 L, one COMPLEX slave of olen = 100 samples at 500 Hz (P = 200), rotated by
+ * shift = 60 bins (150 Hz), and one decision per block (pl_blocksize = 100 = olen).  One launch serves every session that is due, one
+ * workgroup per request: the L samples are converted (:294) and appended to the session's M - 1 old ones, the REAL master and its slave
+ * (chz_rmini_*'s transform and gather rules, the response from the host) leave 100 complex samples, lane t of one wavefront correlates
+ * them with tone t's oscillator in double, in the reference's order (step_osc(), renormalised every 16384 steps; integrator +=
+ * conj(samp) * phasor), and one lane compares the energies |integrator|^2 in ascending tone order with the reference's strict >,
+ * starting from the threshold 0.005 * 100.  The decoder is a recurrence over blocks: the filter's history, the oscillators and the
+ * sticky current tone live on the device, per instance, all zero after chz_ctcss_add (the integrators are zero again after every block).
+ * What stays with the caller: RTP and collecting a stream's packets into rows of L samples.
+ * Limits, refused at chz_ctcss_create / chz_ctcss_check and nowhere else: what chz_rmini_create refuses for that master and slave
+ * (48 kHz gives N = 19200 > 16384; the largest L is 8192, 40960 Hz); a sample rate that is not finite and positive; a byte order that
+ * is neither; a table of fewer than 1 or more than CHZ_CTCSS_TABLE_MAX = 64 tones (one wavefront); a tone that is not finite. */
+#define CHZ_CTCSS_BE 0                /* samples as RTP carries them (ntohs at :294) */
+#define CHZ_CTCSS_LE 1
+#define CHZ_CTCSS_TABLE_MAX 64
+#define CHZ_CTCSS_STANDARD_TONES 55   /* the table searched when chz_ctcss_create is given none: ctcss's own PL_tones[], 67.0 .. 254.1 Hz */
+typedef struct chz_ctcss chz_ctcss;
+typedef struct chz_ctcss_status {
+  int tone_index;               /* the strongest tone above the threshold in this block, -1: none (strongest_tone_index) */
+  int current_index;            /* the last tone found so far (the index of current_pl_tone), -1 before the first detection */
+  double energy;                /* strongest_tone_energy as the block leaves it: the tone's, or the threshold itself when none is found */
+} chz_ctcss_status;
+/* tones: ntones frequencies in Hz, or NULL for the standard table (ntones is then not looked at).  A tone of 0 Hz or below is searched
+ * like any other but never becomes the current one (the reference tests pl_tone > 0, :303). */
+int chz_ctcss_check(double samprate, int byte_order, int ntones, const double *tones);   /* would chz_ctcss_create take this? 0, or < 0 and chz_last_error(); touches no device */
+int chz_ctcss_create(chz_ctcss **out, double samprate, int byte_order, int ntones, const double *tones, int capacity, int device);
+void chz_ctcss_destroy(chz_ctcss *m);
+int chz_ctcss_capacity(const chz_ctcss *m);
+int chz_ctcss_geometry(const chz_ctcss *m, int out7[7]);                         /* L, M, N, olen, P, shift, ntones */
+int chz_ctcss_add(chz_ctcss *m);                                                 /* -> instance index; all state zero, as a fresh session */
+int chz_ctcss_release(chz_ctcss *m, int inst);
+int chz_ctcss_set_response(chz_ctcss *m, int inst, const float *resp);           /* P complex, as chz_rmini_set_response (ctcss: set_filter(-100 / 500, 150 / 500, 11)) */
+/* One block of n decoders, one H2D, ONE launch and one D2H of status records per chunk of `capacity`: instance inst[i] (at most once in
+ * a call) takes the L 16-bit samples at samples[i] in the pool's byte order -- host memory (samples_on_device = 0), or device memory that
+ * is complete before the call (1; read in place, 2-byte aligned).  energies may be NULL; energies[i], where not NULL, receives the
+ * request's ntones energies in table order (a second D2H, made only for a chunk in which a request asks).  Every request is checked
+ * before the first launch: a refused call has written nothing and advanced no state.  Synchronous, thread-safe. */
+int chz_ctcss_execute(chz_ctcss *m, int n, const int *inst, const void *const *samples, int samples_on_device, chz_ctcss_status *status,
+                      double *const *energies);
+
 /* ---- Welch power spectra of the raw input: radiod's wideband spectrum analyser (wideband_poll(), src/spectrum.c:308-522) on the
  * samples the engine's input ring holds (float REAL, float COMPLEX or the int16 of chz_input_write_i16).  A bank holds `capacity`
  * analysers sharing one fft_n (= lrint(samprate / rbw): any length from 8 to 2^20 points; one with a prime factor above 13 runs as

@@ -2282,4 +2282,5 @@ int chz_run_blocks(chz_engine* e, unsigned job0, int nblocks, int mode, int inst
 #include "chz_rmini.inc"
 #include "chz_wfm.inc"
 #include "chz_afsk.inc"
+#include "chz_ctcss.inc"
 #include "chz_welch.inc"

@@ -4013,6 +4013,105 @@ __global__ void __launch_bounds__(1024) afsk_ovs(AfskParams p) {
 }
 
 // ------------------------------------------------------------------------------
+// ctcss's PL tone search (src/ctcss.c:268-309 with process_pl(), :392-419): which of a table of sub-audible tones a session's 16-bit
+// audio carries.  One workgroup per request.  The front is afsk_ovs's: the block's L samples are converted (:294), put behind the
+// session's M - 1 = L old ones (HBM) and run through rmini_ovs's forward transform, split and ONE COMPLEX slave (olen 100, P 200,
+// shift 60: 50 .. 300 Hz spun down by 150 Hz to 500 Hz), whose 100 samples stay in LDS.  Behind the filter nothing feeds back: lane
+// t < ntones of the FIRST wavefront is tone t's correlator and walks the 100 samples in order, in double -- step_osc() (src/osc.c:
+// 61-70, renormalised every 16384 steps), integrator += conj(samp) * phasor (:395) --, then leaves |integrator|^2 in LDS.  pl_blocksize
+// equals olen, so every block ends in exactly one decision and the integrators need no state.  One lane reads the energies in
+// ascending tone order with the reference's strict > (:404-413): ties and NaNs fall as there.
+// LDS: rmini_ovs's, 8 * max(N, N/2 + 1 + 2 P) bytes (24 kHz: 76,800 B); the energies take the first 8 * ntones bytes of the master's
+// bins, which nothing reads after the slave's gather (P <= N makes N/2 >= 100 > 64, so they stay clear of the slave's buffers).
+// ------------------------------------------------------------------------------
+#define CHZ_CTCSS_MAX_TONES 64                 // one wavefront
+struct CtcssState {
+  double ph[CHZ_CTCSS_MAX_TONES][2];           // the oscillators' phasors
+  int steps[CHZ_CTCSS_MAX_TONES];
+  int current1, init;                          // current1: the sticky tone's index + 1 (all zero = a fresh session: no tone yet)
+};
+struct CtcssReq { const unsigned short* samples; int inst, pad; };       // L 16-bit samples (device), any 2-byte alignment
+struct CtcssStatusK { int tone_index, current_index; double energy; };
+struct CtcssParams {
+  const CtcssReq* req;    // [nreq]
+  CtcssState* state;      // [ninst]
+  float* hist;            // [ninst][M - 1]
+  CtcssStatusK* status;   // [nreq]
+  double* energies;       // [nreq][CHZ_CTCSS_MAX_TONES]
+  const double* tone_step;   // [ntones][2] cispi(2 (tone - 150) / 500) (:276)
+  const float2* tw_split; // [N/2 + 1] e^{-2 pi i k / N}
+  MiniParams fwd;         // the N/2-point forward transform
+  RminiSlave sl;          // the COMPLEX slave: m.N = P, m.olen = olen, m.resp = [ninst][P]
+  ChanDesc d;             // its gather (row: the instance, filled in per request)
+  int N, L, ntones, big_endian;
+  unsigned long long positive;   // bit t: tone t > 0 Hz -- only such a tone becomes the current one (:303)
+  double threshold;       // 0.005 * pl_blocksize (:404)
+};
+
+__global__ void __launch_bounds__(1024) ctcss_ovs(CtcssParams p) {
+  HIP_DYNAMIC_SHARED(float2, lds)
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int N = p.N, H = N / 2, L = p.L, Mm1 = N - L, P = p.sl.m.N, olen = p.sl.m.olen;
+  const CtcssReq rq = p.req[blockIdx.x];
+  // ---- the window: M - 1 old samples, then the block's L (:294: host order, scaled by 2^-15 -- exact in a float)
+  float* Af = reinterpret_cast<float*>(lds);
+  float* __restrict__ hist = p.hist + (size_t)rq.inst * Mm1;
+  for (int n = tid; n < Mm1; n += nthr) Af[n] = hist[n];
+  for (int n = tid; n < L; n += nthr) {
+    unsigned v = rq.samples[n];
+    if (p.big_endian) v = ((v & 0xffu) << 8) | (v >> 8);
+    Af[Mm1 + n] = (float)(short)v * (1.0f / 32768.0f);
+  }
+  __syncthreads();
+  for (int n = tid; n < Mm1; n += nthr) hist[n] = Af[L + n];               // the window's last M - 1 samples are the next block's old ones
+  __syncthreads();
+  // ---- the filter (:295-299): rmini_ovs's forward transform, split and slave
+  float2* A = lds;
+  float2* B = lds + H;
+  const float2* Z = mini_fft<-1>(A, B, p.fwd, tid, nthr);
+  float2* S = lds;
+  rmini_split(Z, S, p.tw_split, H, tid, nthr);
+  float2* Y = lds + H + 1;
+  const int no_isb = 0;
+  ChanDesc d = p.d; d.row = rq.inst;
+  const float2* T = rmini_slave(S, Y, p.sl, d, no_isb, H + 1, tid, nthr) + (P - olen);      // the last olen of the P samples
+  // ---- the correlators (:394-395): lane t is tone t
+  double* E = reinterpret_cast<double*>(lds);
+  CtcssState* st = p.state + rq.inst;
+  if (tid < p.ntones) {
+    double ph[2] = {st->ph[tid][0], st->ph[tid][1]};
+    int steps = st->steps[tid];
+    if (!st->init) { ph[0] = 1.0; ph[1] = 0.0; steps = CHZ_AFSK_RENORM; }   // a fresh session: set_osc() on a zeroed struct osc
+    const double step[2] = {p.tone_step[2 * tid], p.tone_step[2 * tid + 1]};
+    double ar = 0.0, ai = 0.0;
+    for (int n = 0; n < olen; n++) {
+      const double xr = (double)T[n].x, xi = (double)T[n].y;
+      double cr, ci;
+      afsk_step_osc(ph, steps, step, cr, ci);
+      ar += xr * cr + xi * ci; ai += xr * ci - xi * cr;                    // conj(samp) * phasor
+    }
+    st->ph[tid][0] = ph[0]; st->ph[tid][1] = ph[1]; st->steps[tid] = steps;
+    const double e = ar * ar + ai * ai;                                    // cnrm() (:407)
+    E[tid] = e;
+    p.energies[(size_t)blockIdx.x * CHZ_CTCSS_MAX_TONES + tid] = e;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  // ---- the decision (:404-415), one lane in ascending tone order
+  CtcssStatusK so;
+  so.energy = p.threshold; so.tone_index = -1;
+  for (int n = 0; n < p.ntones; n++) {
+    const double e = E[n];
+    if (e > so.energy) { so.energy = e; so.tone_index = n; }
+  }
+  int current1 = st->current1;
+  if (so.tone_index >= 0 && ((p.positive >> so.tone_index) & 1)) current1 = so.tone_index + 1;
+  so.current_index = current1 - 1;
+  st->current1 = current1; st->init = 1;
+  p.status[blockIdx.x] = so;
+}
+
+// ------------------------------------------------------------------------------
 // K3+K4 for ANY P without a prime factor above 13 -- the sizes the register-tiled chan_ifft / chan_c2r menu does not hold
 // (wfm's 384 kHz channel on a 20 ms block with overlap 5 is P = 9600, src/wfm.c:37-39; odd sample rates).  One workgroup
 // per channel: the gather x response of src/filter.c:728-911 lands in LDS in FFT order (COMPLEX or REAL output, ISB

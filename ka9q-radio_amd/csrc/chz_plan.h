@@ -559,4 +559,30 @@ inline int afsk_check_geom(int L, int M, double samprate, double bitrate, double
   return 0;
 }
 
+// ---- pooled CTCSS / PL tone decoders (ctcss_ovs): ctcss's geometry from the sample rate alone (src/ctcss.c:268-298) ----------------------
+// out7: L = lrint(0.2 samprate), M = L + 1, N = 2 L, olen = lrint(500 * 0.2) = 100, P = N olen / L = 200, shift = lrint(2 * 150 * 0.2) = 60,
+// ntones.  Refuses what rmini_check_geom refuses for that REAL master with its one COMPLEX slave, a table of fewer than 1 or more than 64
+// tones (one wavefront) and a tone that is not finite; tones == nullptr stands for the reference's own table.
+#define CHZ_CTCSS_TONES_MAX 64
+#define CHZ_CTCSS_PL_SAMPRATE 500.0              // PL_samprate
+#define CHZ_CTCSS_PL_SHIFT 150.0                 // PL_Shift
+#define CHZ_CTCSS_FILTER_TIME 0.2                // Filter_time = 1 / PL_blockrate
+inline int ctcss_check_geom(double samprate, int ntones, const double* tones, int out7[7], char* why, size_t why_len) {
+  if (!(samprate > 0) || !(samprate < 1e9)) { snprintf(why, why_len, "bad CTCSS sample rate %g", samprate); return -1; }
+  if (ntones < 1 || ntones > CHZ_CTCSS_TONES_MAX) { snprintf(why, why_len, "a CTCSS pool searches 1 to 64 tones (got %d)", ntones); return -1; }
+  if (tones)
+    for (int t = 0; t < ntones; t++)
+      if (!std::isfinite(tones[t])) { snprintf(why, why_len, "tone %d of the table is not finite", t); return -1; }
+  const int L = (int)lrint(CHZ_CTCSS_FILTER_TIME * samprate), M = L + 1;
+  const int olen[1] = {(int)lrint(CHZ_CTCSS_PL_SAMPRATE * CHZ_CTCSS_FILTER_TIME)}, type[1] = {CHZ_IN_COMPLEX};
+  int P[1] = {};
+  const int rc = rmini_check_geom(L, M, 1, olen, type, P, why, why_len);
+  if (rc) return rc;
+  if (out7) {
+    out7[0] = L; out7[1] = M; out7[2] = L + M - 1; out7[3] = olen[0]; out7[4] = P[0];
+    out7[5] = (int)lrint(2 * (CHZ_CTCSS_PL_SHIFT * CHZ_CTCSS_FILTER_TIME)); out7[6] = ntones;
+  }
+  return 0;
+}
+
 }  // namespace chz

@@ -63,7 +63,18 @@ class AfskStatus(C.Structure):
                 ("flag_seen", _i), ("frame_bits", _i), ("crc_failures", _i), ("nframes", _i), ("frame_len", _i * 2)]
 
 
+class CtcssStatus(C.Structure):
+    """chz_ctcss_status: one block of one PL tone decoder (indices into the pool's tone table, -1: none)."""
+    _fields_ = [("tone_index", _i), ("current_index", _i), ("energy", _d)]
+
+
 AFSK_BE, AFSK_LE = 0, 1
+CTCSS_BE, CTCSS_LE = 0, 1
+CTCSS_TABLE_MAX = 64
+# the table a CtcssPool searches when it is given none: ctcss's own (src/ctcss.c:62-69)
+CTCSS_TONES = (67.0, 69.3, 71.9, 74.4, 77.0, 79.7, 82.5, 85.4, 88.5, 91.5, 94.8, 97.4, 100.0, 103.5, 107.2, 110.9, 114.8, 118.8, 123.0, 127.3,
+               131.8, 136.5, 141.3, 146.2, 150.0, 151.4, 156.7, 159.8, 162.2, 165.5, 167.9, 171.3, 173.8, 177.3, 179.9, 183.5, 186.2, 189.9, 192.8,
+               196.6, 199.5, 203.5, 206.5, 210.7, 213.8, 218.1, 221.3, 225.7, 229.1, 233.6, 237.1, 241.8, 245.5, 250.3, 254.1)
 AFSK_FRAME_MAX = 16384
 PCM_S16BE, PCM_S16LE, PCM_F32LE, PCM_F32BE, PCM_MULAW, PCM_ALAW, PCM_F16LE, PCM_F16BE = 0, 1, 2, 3, 4, 5, 6, 7
 FLAG_NO_SAMPLES, FLAG_MUTE, FLAG_PLL_LOCK, FLAG_TONE_MUTE, FLAG_PENDING = 1, 2, 4, 8, 16
@@ -91,6 +102,8 @@ SYMBOLS = [
     "chz_wfm_set_response", "chz_wfm_execute",
     "chz_afsk_check", "chz_afsk_create", "chz_afsk_destroy", "chz_afsk_capacity", "chz_afsk_geometry", "chz_afsk_add", "chz_afsk_release",
     "chz_afsk_set_response", "chz_afsk_execute",
+    "chz_ctcss_check", "chz_ctcss_create", "chz_ctcss_destroy", "chz_ctcss_capacity", "chz_ctcss_geometry", "chz_ctcss_add", "chz_ctcss_release",
+    "chz_ctcss_set_response", "chz_ctcss_execute",
     "chz_comm_barrier", "chz_comm_allreduce_max", "chz_spectrum_broadcast", "chz_spectrum_exchange_rows", "chz_run_blocks_sharded",
     "chz_comm_create_local", "chz_spectrum_broadcast_local", "chz_set_option",
     "chz_welch_create", "chz_welch_destroy", "chz_welch_set_window", "chz_welch_configure", "chz_welch_poll", "chz_welch_read", "chz_welch_read_async",
@@ -188,6 +201,15 @@ def lib():
         L.chz_afsk_release.argtypes = [_vp, _i]
         L.chz_afsk_set_response.argtypes = [_vp, _i, _vp]
         L.chz_afsk_execute.argtypes = [_vp, _i, _vp, _vp, _i, _vp, _vp, _i]
+        L.chz_ctcss_check.argtypes = [_d, _i, _i, _vp]
+        L.chz_ctcss_create.argtypes = [C.POINTER(_vp), _d, _i, _i, _vp, _i, _i]
+        L.chz_ctcss_destroy.argtypes = [_vp]; L.chz_ctcss_destroy.restype = None
+        L.chz_ctcss_capacity.argtypes = [_vp]
+        L.chz_ctcss_geometry.argtypes = [_vp, C.POINTER(_i * 7)]
+        L.chz_ctcss_add.argtypes = [_vp]
+        L.chz_ctcss_release.argtypes = [_vp, _i]
+        L.chz_ctcss_set_response.argtypes = [_vp, _i, _vp]
+        L.chz_ctcss_execute.argtypes = [_vp, _i, _vp, _vp, _i, _vp, _vp]
         L.chz_comm_unique_id.argtypes = [_vp]
         L.chz_comm_create.argtypes = [C.POINTER(_vp), _i, _i, _vp, _i]
         L.chz_comm_create_file.argtypes = [C.POINTER(_vp), _i, _i, C.c_char_p, _i, _d]
@@ -997,6 +1019,79 @@ class AfskPool:
     def close(self):
         if self._h:
             lib().chz_afsk_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CtcssPool:
+    """Pool of CTCSS / PL tone decoders of one sample rate, byte order and tone table (ctcss's tone search, src/ctcss.c): 16-bit audio in
+    rows of L = 0.2 s, one status record per block out -- the strongest tone above the threshold, the last tone found, its energy -- and, on
+    request, the energies of all tones.  RTP and collecting packets into rows stay with the caller."""
+
+    def __init__(self, samprate, capacity, byte_order=CTCSS_BE, tones=None, device=0):
+        self._h = _vp()
+        n, t = self._table(tones)
+        _check(lib().chz_ctcss_create(C.byref(self._h), float(samprate), byte_order, n, t, capacity, device))
+        g = (_i * 7)()
+        _check(lib().chz_ctcss_geometry(self._h, C.byref(g)))
+        self.geometry = dict(zip(("L", "M", "N", "olen", "P", "shift", "ntones"), (int(v) for v in g)))
+        self.L, self.M, self.N, self.olen, self.P, self.shift, self.ntones = (int(v) for v in g)
+        self.tones = tuple(CTCSS_TONES if tones is None else (float(f) for f in tones))
+        self.samprate, self.capacity, self.byte_order = float(samprate), capacity, byte_order
+
+    @staticmethod
+    def _table(tones):
+        if tones is None:
+            return 0, None
+        tones = [float(f) for f in tones]
+        return len(tones), (_d * max(len(tones), 1))(*tones)
+
+    @staticmethod
+    def check(samprate, byte_order=CTCSS_BE, tones=None):
+        """Would a pool of this geometry be created?  Raises ChzError with the reason if not; touches no device."""
+        n, t = CtcssPool._table(tones)
+        _check(lib().chz_ctcss_check(float(samprate), byte_order, n, t))
+
+    def add(self):
+        return _check(lib().chz_ctcss_add(self._h))
+
+    def release(self, inst):
+        _check(lib().chz_ctcss_release(self._h, inst))
+
+    def set_response(self, inst, resp):
+        r = np.ascontiguousarray(resp, np.complex64).reshape(-1)
+        assert r.shape[0] == self.P
+        _check(lib().chz_ctcss_set_response(self._h, inst, r.ctypes.data))
+
+    def execute(self, insts, samples, on_device=False, status_buf=None, energies=None):
+        """samples: [n][L] 16-bit words in the pool's byte order as they lie in memory (an int16 / uint16 array or a list of n rows, of which
+        one may be None: a null row, which the call refuses), or (on_device) n device addresses of L such words each, complete before the call.
+        status_buf: the caller's own uint8 buffer [n][sizeof(CtcssStatus)] (a caller that runs every block keeps it; without it each call makes
+        its own).  energies: None, or a float64 array [n][ntones] that receives every request's energies.  -> CtcssStatus array."""
+        insts = np.ascontiguousarray(insts, np.int32)
+        n = insts.shape[0]
+        if on_device:
+            sp = (_vp * n)(*[int(a) if a else None for a in samples])
+        else:
+            rows = [None if r is None else np.ascontiguousarray(r).view(np.uint16).reshape(self.L) for r in samples]
+            sp = (_vp * n)(*[None if r is None else r.ctypes.data for r in rows])
+        sraw = np.empty((n, C.sizeof(CtcssStatus)), np.uint8) if status_buf is None else status_buf
+        assert sraw.dtype == np.uint8 and sraw.flags.c_contiguous and sraw.shape == (n, C.sizeof(CtcssStatus))
+        ep = None
+        if energies is not None:
+            assert energies.dtype == np.float64 and energies.flags.c_contiguous and energies.shape == (n, self.ntones)
+            ep = (_vp * n)(*[energies[i].ctypes.data for i in range(n)])
+        _check(lib().chz_ctcss_execute(self._h, n, insts.ctypes.data, sp, int(bool(on_device)), sraw.ctypes.data, ep))
+        return (CtcssStatus * n).from_buffer(sraw)
+
+    def close(self):
+        if self._h:
+            lib().chz_ctcss_destroy(self._h)
             self._h = _vp()
 
     def __del__(self):

@@ -1,0 +1,403 @@
+"""Pools of CTCSS / PL tone decoders (chz_ctcss_*, kernel ctcss_ovs) against tests/ctcss_oracle.py, the float64 restatement of ctcss's tone
+search that tests/test_ctcss_reference.py pins to the reference.
+
+Two shapes -- ctcss's documented one (24 kHz: L 4800, N 9600, 76,800 B of LDS: the large-LDS path) and the smallest rate a PCM stream has
+(8 kHz: L 1600, N 3200) -- each run ONE scenario of four instances in a big-endian pool of capacity 2 (two launches per call while all
+are due), the order permuted from call to call, and a fifth in a little-endian pool:
+  0  the 55 standard tones in table order, three blocks each, phase continuous, amplitude 0.05 + 0.01 (k mod 7); 2 blocks of zeros; 100 Hz
+     at 0.005 (below the threshold, which is amplitude 0.01) for 2 blocks and at 0.012 for 2; 1 block of zeros; 203.5 Hz at 0.9 for 3.
+     175 blocks; the 16384th oscillator step, the first renormalisation, falls in block 163
+  1  two simultaneous tones of unequal amplitude in seeded white noise, the pair changing every three blocks (36 blocks)
+  2  a +-full-scale square wave of 100 Hz with -32768 in it, blocks of exact zeros, a tone that starts in the middle of a block (12 blocks)
+  3  the samples of instance 0 handed over in device memory
+  4  the samples of instance 1 in little-endian words
+The scenario and its restatement (float64, and the f32 twin) are computed once per shape and shared by the tests.
+
+Bounds, on EVERY block: tone_index and current_index equal the restatement's.  Every energy: the rule of tests/test_gpu_wfm.py -- within
+1e-6 relative to the block's largest energy, or 4 x the f32 twin's own distance on that block (the largest distance of any of the block's
+energies between the restatement's float64 and float32 runs: what rounding alone moves in that block) where that is larger.  The status
+record's energy is held to the same rule (it is the strongest energy, or the threshold itself, exactly).  A block whose energies are all
+exactly zero in the restatement (a window of zeros) must be exactly zero on the device.  The tests print the worst measured / allowed.
+Input condition, asserted on the restatement before anything is compared, with no block exempt: the strongest energy differs from the
+threshold by more than FLOOR x the threshold, and from the runner-up by more than FLOOR x the strongest, where FLOOR = 100 x the largest
+distance between the restatement's float64 and float32 runs on an energy relative to its block's strongest.  The runner-up half is asked
+of every block whose strongest energy exceeds the threshold: below the threshold the comparison at src/ctcss.c:408 never succeeds, the
+order of the energies decides nothing, and a window of exact zeros (instance 0 has such blocks by definition) makes all 55 energies
+equal.  Measured on the restatement for instance 0: FLOOR 1.35e-5 / 1.69e-5 at 24 / 8 kHz, the smallest margin 8.6e-5 / 9.0e-5 (5 to 6 x FLOOR), both
+in block 75, where the sweep moves from 150.0 to 151.4 Hz (the tone generator's phase rule decides that figure; the block is the one expected).
+The tests print every instance's figures; on the MI355X the worst measured / allowed is 0.69 (instance 2 at 8 kHz)."""
+import functools
+
+import numpy as np
+import pytest
+
+import afsk_oracle as ao
+import ctcss_oracle as co
+import oracle_lib as ol
+from conftest import load_pkg
+from test_gpu_afsk import DeviceRows
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = {"24k": 24000.0, "8k": 8000.0}
+CAP = 2
+SENTINEL = 0xA5
+STATUS_BYTES = 16
+T = co.TONES
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    p = load_pkg()
+    if p.engine.lib().chz_device_count() < 1:
+        pytest.fail("no HIP device visible: GPU tests cannot run (there is no CPU fallback)")
+    ol.build()
+    return p
+
+
+# instance 1: (stronger tone, weaker tone) by table index, three blocks each; amplitudes 0.2 and 0.07, noise of 0.01 rms
+PAIRS = [(12, 40), (3, 30), (24, 0), (54, 25), (41, 8), (17, 50), (0, 54), (33, 20), (47, 5), (25, 44), (9, 37), (52, 14)]
+
+
+def instance1(fs):
+    return co.generate(fs, [(3, [(T[a], 0.2), (T[b], 0.07)], 0.01) for a, b in PAIRS], seed=21)
+
+
+def instance2(fs):
+    L = co.geometry(fs)["L"]
+    half = int(fs / 200)                                                    # half a period of 100 Hz
+    sq = np.where((np.arange(3 * L) // half) % 2 == 0, 32767, -32768).astype(np.int16).reshape(3, L)
+    late = co.generate(fs, [(4, [(136.5, 0.3)], 0.0)])
+    late = np.concatenate([np.zeros(L // 2, np.int16), late.reshape(-1)[:3 * L + L // 2]]).reshape(4, L)      # the tone starts mid-block
+    return np.concatenate([sq, np.zeros((3, L), np.int16), late, np.zeros((2, L), np.int16)])
+
+
+@functools.lru_cache(maxsize=None)
+def scenario(shape):
+    """int16 blocks [nblocks][L] of instances 0-2"""
+    fs = SHAPES[shape]
+    return [co.instance0(fs), instance1(fs), instance2(fs)]
+
+
+@functools.lru_cache(maxsize=None)
+def restatement(shape, f32):
+    return [co.run(b, SHAPES[shape], f32=f32) for b in scenario(shape)]
+
+
+def input_condition(ref, twin, label):
+    """see the module's docstring -> (FLOOR, smallest margin relative to what it is a margin of, its block)"""
+    dist = 0.0
+    for r, t in zip(ref, twin):
+        top = float(r["energies"].max())
+        if top > 0:
+            dist = max(dist, float(np.abs(r["energies"] - t["energies"]).max()) / top)
+    floor = 100.0 * dist
+    smallest, where = np.inf, -1
+    for blk, r in enumerate(ref):
+        e = np.sort(r["energies"])[::-1]
+        margins = [abs(float(e[0]) - co.THRESHOLD) / co.THRESHOLD]
+        if e[0] > co.THRESHOLD and e.size > 1:
+            margins.append(float(e[0] - e[1]) / float(e[0]))
+        for m in margins:
+            assert m > floor, (label, blk, "a decision within FLOOR of a tie: unusable input", m, floor)
+            if m < smallest:
+                smallest, where = m, blk
+    return floor, smallest, where
+
+
+def check(ref, twin, got, label):
+    """got: list over blocks of (status, energies) -> prints FLOOR, the smallest margin and the worst measured / allowed"""
+    floor, smallest, where = input_condition(ref, twin, label)
+    assert len(got) == len(ref)
+    worst = 0.0
+    for blk, (r, t, (st, en)) in enumerate(zip(ref, twin, got)):
+        assert st.tone_index == r["tone_index"] and st.current_index == r["current_index"], (label, blk, st.tone_index, r["tone_index"], st.current_index, r["current_index"])
+        top = float(r["energies"].max())
+        if top == 0.0:
+            assert not en.any() and st.energy == co.THRESHOLD, (label, blk)
+            continue
+        lim = max(1e-6, 4 * float(np.abs(t["energies"] - r["energies"]).max()) / top)
+        e = max(float(np.abs(en - r["energies"]).max()), abs(st.energy - r["energy"])) / top
+        worst = max(worst, e / lim)
+        assert e <= lim, (label, blk, e, lim)
+        assert st.energy == (en[st.tone_index] if st.tone_index >= 0 else co.THRESHOLD), (label, blk)
+    print("%s: FLOOR %.3g, smallest margin %.3g (block %d, %.0f x FLOOR); worst measured / allowed %.2f over %d blocks"
+          % (label, floor, smallest, where, smallest / floor if floor else np.inf, worst, len(ref)))
+
+
+def buffers(n, ntones=len(T)):
+    """the caller's status and energies buffers of n requests, full of the sentinel"""
+    return np.full((n, STATUS_BYTES), SENTINEL, np.uint8), np.full((n, ntones * 8), SENTINEL, np.uint8).view(np.float64)
+
+
+def untouched(sraw, en):
+    return (sraw == SENTINEL).all() and (en.view(np.uint8) == SENTINEL).all()
+
+
+def run_pool(pkg, shape, cap, src, device=(), big_endian=True, seed=7, energies=True, tones=None):
+    """src: {k: int16 blocks}; the instances in `device` hand their samples over in device memory.
+    -> {k: list over blocks of (CtcssStatus copy, energies, raw status bytes)}"""
+    fs = SHAPES[shape] if isinstance(shape, str) else shape
+    E = pkg.engine
+    ks = list(src)
+    pool = E.CtcssPool(fs, cap, byte_order=E.CTCSS_BE if big_endian else E.CTCSS_LE, tones=tones)
+    dev = {}
+    try:
+        L, nt = pool.L, pool.ntones
+        resp = co.response(fs)
+        inst = {k: pool.add() for k in ks}
+        for k in ks:
+            pool.set_response(inst[k], resp)
+        dev = {k: DeviceRows(ao.to_wire(src[k], big_endian)) for k in device}
+        rng = np.random.default_rng(seed)
+        out = {k: [] for k in ks}
+        for blk in range(max(len(src[k]) for k in ks)):
+            due = [k for k in ks if blk < len(src[k])]
+            order = [due[i] for i in rng.permutation(len(due))]
+            for group, on_device in (([k for k in order if k not in dev], False), ([k for k in order if k in dev], True)):
+                if not group:
+                    continue
+                rows = [dev[k].row(blk, L) for k in group] if on_device else [ao.to_wire(src[k][blk], big_endian) for k in group]
+                sraw, en = buffers(len(group), nt)
+                st = pool.execute([inst[k] for k in group], rows, on_device=on_device, status_buf=sraw, energies=en if energies else None)
+                for r, k in enumerate(group):
+                    s = E.CtcssStatus(st[r].tone_index, st[r].current_index, st[r].energy)
+                    out[k].append((s, en[r].copy(), sraw[r].tobytes()))
+        return out
+    finally:
+        pool.close()
+        for d in dev.values():
+            d.free()
+
+
+_device_runs = {}
+
+
+def device_run(pkg, shape):
+    """the scenario's big-endian pool: instances 0-2 and 3 (instance 0's samples in device memory)"""
+    if shape not in _device_runs:
+        b = scenario(shape)
+        _device_runs[shape] = run_pool(pkg, shape, CAP, {0: b[0], 1: b[1], 2: b[2], 3: b[0]}, device=(3,))
+    return _device_runs[shape]
+
+
+def pairs(run):
+    return [(s, e) for s, e, _ in run]
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_geometry(pkg, shape):
+    fs = SHAPES[shape]
+    pool = pkg.engine.CtcssPool(fs, CAP)
+    try:
+        assert pool.geometry == co.geometry(fs) and pool.geometry["L"] == {"24k": 4800, "8k": 1600}[shape]
+        assert pool.tones == co.TONES == pkg.engine.CTCSS_TONES
+        assert pkg.engine.lib().chz_ctcss_capacity(pool._h) == CAP
+    finally:
+        pool.close()
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_every_standard_tone_in_table_order_the_threshold_and_the_first_renormalisation(pkg, shape):
+    ref = restatement(shape, False)[0]
+    assert len(ref) == 175
+    for k in range(len(T)):                                                 # the input does what it is meant to do, in the restatement
+        assert [r["tone_index"] for r in ref[3 * k + 1:3 * k + 3]] == [k, k], (shape, k)
+    # the tail: tone 54 rings out, zeros, 100 Hz below the threshold, then above it (the filter delays it by half a block), zeros, 203.5 Hz
+    assert [r["tone_index"] for r in ref[165:175]] == [54, -1, -1, -1, -1, 12, -1, 41, 41, 41]
+    assert [r["current_index"] for r in ref[165:175]] == [54, 54, 54, 54, 54, 12, 12, 41, 41, 41] and ref[0]["current_index"] in (-1, 0)
+    assert not ref[166]["energies"].any() and ref[166]["energy"] == co.THRESHOLD == 0.5
+    check(ref, restatement(shape, True)[0], pairs(device_run(pkg, shape)[0]), "%s instance 0" % shape)
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_two_tones_of_unequal_amplitude_in_noise(pkg, shape):
+    ref = restatement(shape, False)[1]
+    for k, (a, b) in enumerate(PAIRS):
+        assert [r["tone_index"] for r in ref[3 * k + 1:3 * k + 3]] == [a, a], (shape, k)
+    check(ref, restatement(shape, True)[1], pairs(device_run(pkg, shape)[1]), "%s instance 1" % shape)
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_full_scale_square_wave_exact_zeros_and_a_tone_from_mid_block(pkg, shape):
+    blocks = scenario(shape)[2]
+    assert blocks.min() == -32768 and blocks.max() == 32767
+    ref = restatement(shape, False)[2]
+    assert [r["tone_index"] for r in ref[1:3]] == [12, 12] and not ref[5]["energies"].any() and ref[8]["tone_index"] == 21
+    check(ref, restatement(shape, True)[2], pairs(device_run(pkg, shape)[2]), "%s instance 2" % shape)
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_samples_in_device_memory_give_the_same_bytes(pkg, shape):
+    got = device_run(pkg, shape)
+    assert len(got[3]) == len(got[0]) == 175
+    for blk, (a, b) in enumerate(zip(got[0], got[3])):
+        assert a[2] == b[2] and a[1].tobytes() == b[1].tobytes(), (shape, blk)
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_little_endian_samples(pkg, shape):
+    be = device_run(pkg, shape)[1]
+    le = run_pool(pkg, shape, CAP, {1: scenario(shape)[1]}, big_endian=False)[1]
+    assert len(le) == len(be)
+    for blk, (a, b) in enumerate(zip(be, le)):
+        assert a[2] == b[2] and a[1].tobytes() == b[1].tobytes(), (shape, blk)
+
+
+def test_released_and_added_again_starts_from_zero(pkg):
+    shape = "8k"
+    fs = SHAPES[shape]
+    blocks = scenario(shape)[0]
+    pool = pkg.engine.CtcssPool(fs, CAP)
+    try:
+        resp = co.response(fs)
+        other = pool.add()
+        i = pool.add()
+        pool.set_response(i, resp)
+        for blk in range(0, 171):                                           # leave it past the first renormalisation, with history and a current tone
+            st = pool.execute([i], [ao.to_wire(blocks[blk])])
+        assert st[0].tone_index == st[0].current_index == 12 and blocks[170].any()
+        pool.release(i)
+        j = pool.add()
+        assert j == i and other != i
+        pool.set_response(j, resp)
+        # a block of zeros shows both: old history would leave energy in it, an old current tone would still be reported
+        _, en = buffers(1)
+        st = pool.execute([j], [np.zeros(pool.L, np.uint16)], energies=en)
+        assert (st[0].tone_index, st[0].current_index, st[0].energy) == (-1, -1, co.THRESHOLD) and not en.any()
+        pool.release(j)
+        assert pool.add() == j
+        pool.set_response(j, resp)
+        got = []
+        for blk in range(len(blocks)):
+            _, en = buffers(1)
+            st = pool.execute([j], [ao.to_wire(blocks[blk])], energies=en)
+            got.append((pkg.engine.CtcssStatus(st[0].tone_index, st[0].current_index, st[0].energy), en[0].copy()))
+        check(restatement(shape, False)[0], restatement(shape, True)[0], got, "8k instance 0 after release and add")
+    finally:
+        pool.close()
+
+
+def test_refused_calls_leave_state_and_outputs_untouched(pkg):
+    """an instance listed twice, an index that is not in use, one out of range and a null row among good requests, each between two good blocks of
+    instance 1: status and energies buffers keep the sentinel, and the run matches the restatement as if nothing had happened"""
+    shape = "8k"
+    fs = SHAPES[shape]
+    blocks = scenario(shape)[1]
+    E = pkg.engine
+    pool = E.CtcssPool(fs, CAP)
+    try:
+        resp = co.response(fs)
+        a, b = pool.add(), pool.add()
+        pool.set_response(a, resp); pool.set_response(b, resp)
+        pool.release(b)
+        got = []
+        for blk in range(len(blocks)):
+            row = ao.to_wire(blocks[blk])
+            bad = {20: ([a, a], [row, row], "twice"), 21: ([a, b], [row, row], "not in use"), 22: ([a, 99], [row, row], "bad request"),
+                   23: ([a, a], [row, None], "bad request")}.get(blk)
+            if bad:
+                sraw, en = buffers(2)
+                with pytest.raises(E.ChzError) as e:
+                    pool.execute(bad[0], bad[1], status_buf=sraw, energies=en)
+                assert bad[2] in str(e.value), str(e.value)
+                assert untouched(sraw, en)
+            _, en = buffers(1)
+            st = pool.execute([a], [row], energies=en)
+            got.append((E.CtcssStatus(st[0].tone_index, st[0].current_index, st[0].energy), en[0].copy()))
+        check(restatement(shape, False)[1], restatement(shape, True)[1], got, "8k instance 1 between refused calls")
+    finally:
+        pool.close()
+
+
+NAN, INF = float("nan"), float("inf")
+REFUSALS = [((48000.0, None), "16384"),                                     # what chz_rmini_check refuses: N = 19200
+            ((40965.0, None), "16384"),                                     # L 8193: the first beyond the largest
+            ((8500.0, None), "prime factor"),                               # L 1700 = 17 x 100
+            ((100.0, None), "olen"),                                        # L 20: the slave's 100 samples do not fit
+            ((NAN, None), "sample rate"), ((INF, None), "sample rate"), ((0.0, None), "sample rate"), ((-8000.0, None), "sample rate"),
+            ((8000.0, []), "1 to 64"), ((8000.0, [100.0 + k for k in range(65)]), "1 to 64"),
+            ((8000.0, [100.0, NAN]), "not finite"), ((8000.0, [INF]), "not finite"),
+            ((40960.0, None), None),                                        # L 8192, N 16384: the largest that fits
+            ((8000.0, [100.0 + k for k in range(64)]), None)]
+
+
+@pytest.mark.parametrize("geom,word", REFUSALS)
+def test_geometries_that_are_refused(pkg, geom, word):
+    E = pkg.engine
+    fs, tones = geom
+    if word is None:
+        E.CtcssPool.check(fs, tones=tones)
+        return
+    for make in (lambda: E.CtcssPool.check(fs, tones=tones), lambda: E.CtcssPool(fs, CAP, tones=tones)):
+        with pytest.raises(E.ChzError) as e:
+            make()
+        assert word in str(e.value), str(e.value)
+
+
+def test_a_byte_order_that_is_neither_is_refused(pkg):
+    E = pkg.engine
+    for make in (lambda: E.CtcssPool.check(8000.0, byte_order=2), lambda: E.CtcssPool(8000.0, CAP, byte_order=-1)):
+        with pytest.raises(E.ChzError) as e:
+            make()
+        assert "byte order" in str(e.value), str(e.value)
+
+
+def test_capacity_8_gives_the_same_bytes(pkg):
+    shape = "8k"
+    got = device_run(pkg, shape)
+    b = scenario(shape)
+    again = run_pool(pkg, shape, 8, {0: b[0], 1: b[1], 2: b[2], 3: b[0]}, device=(3,))
+    for k in range(4):
+        assert len(again[k]) == len(got[k])
+        for blk, (x, y) in enumerate(zip(got[k], again[k])):
+            assert x[2] == y[2] and x[1].tobytes() == y[1].tobytes(), (k, blk)
+
+
+def test_without_energies_the_status_bytes_are_the_same(pkg):
+    shape = "8k"
+    got = device_run(pkg, shape)
+    b = scenario(shape)
+    again = run_pool(pkg, shape, CAP, {1: b[1], 2: b[2]}, energies=False)
+    for k in (1, 2):
+        for blk, (x, y) in enumerate(zip(got[k], again[k])):
+            assert x[2] == y[2], (k, blk)
+            assert (y[1].view(np.uint8) == SENTINEL).all()                  # the caller's energies buffer was never handed over
+
+
+MORE = (55.0, 60.5, 258.0, 262.5, 268.0, 275.0, 281.5, 288.0, 295.0)         # nine more inside the 50 .. 300 Hz passband
+TABLES = {"1": (103.5,), "64": T + MORE}
+
+
+@functools.lru_cache(maxsize=None)
+def table_blocks():
+    seg = [(2, [(103.5, 0.1)], 0.0), (2, [(275.0, 0.2)], 0.0), (1, [], 0.0), (2, [(60.5, 0.15), (131.8, 0.05)], 0.0), (2, [(103.5, 0.004)], 0.0), (1, [(295.0, 0.3)], 0.0)]
+    return co.generate(SHAPES["8k"], seg)
+
+
+@pytest.mark.parametrize("table", list(TABLES))
+def test_a_custom_tone_table(pkg, table):
+    tones = TABLES[table]
+    assert len(tones) == int(table)
+    blocks = table_blocks()
+    ref, twin = (co.run(blocks, SHAPES["8k"], f32=f, tones=tones) for f in (False, True))
+    if table == "64":
+        assert [r["tone_index"] for r in ref] == [13, 13, 60, 60, 60, 56, 56, 56, -1, 63]      # (a block of zeros still holds the tone's tail)
+    else:
+        assert [r["tone_index"] for r in ref] == [0, 0, 0, -1, -1, -1, -1, -1, -1, -1]
+    got = run_pool(pkg, "8k", CAP, {0: blocks}, tones=tones)[0]
+    assert all(en.shape == (len(tones),) for _, en, _ in got)
+    check(ref, twin, pairs(got), "8k table of %s" % table)
+
+
+def test_ten_blocks_at_32_kHz_the_largest_lds_need_that_is_run(pkg):
+    """24 kHz already needs more than 64 KB of LDS (8 N = 76,800 B); 32 kHz is 102,400 B with 1024 threads"""
+    fs = 32000.0
+    g = co.geometry(fs)
+    assert 8 * max(g["N"], g["N"] // 2 + 1 + 2 * g["P"]) == 102400 > 64 * 1024
+    blocks = co.generate(fs, [(3, [(T[5], 0.1)], 0.0), (3, [(T[30], 0.2), (T[50], 0.05)], 0.005), (1, [], 0.0), (3, [(T[54], 0.5)], 0.0)], seed=5)
+    assert len(blocks) == 10
+    ref, twin = (co.run(blocks, fs, f32=f) for f in (False, True))
+    assert [r["tone_index"] for r in ref] == [5, 5, 5, 30, 30, 30, 30, 54, 54, 54]
+    got = run_pool(pkg, fs, CAP, {0: blocks})[0]
+    check(ref, twin, pairs(got), "32 kHz")
