@@ -370,6 +370,23 @@ int chz_bank_read_pcm_flags_async(chz_engine *e, int bank, int slot, int ch0, in
    without waiting for later blocks already handed to the demodulator stream (a double-buffered host loop waits for block j-1
    here while block j runs) */
 int chz_bank_pcm_wait(chz_engine *e, int bank, int slot);
+/* ---- only the rows somebody will send.  A channel is OPEN on a slot when its demodulator is on and its flag byte has none of
+ * CHZ_FLAG_NO_SAMPLES, CHZ_FLAG_MUTE and CHZ_FLAG_PENDING: send_output() is handed samples for these and for no others.  The device
+ * gathers their rows (kernels pcm_open_count / pcm_open_rows), so that n flag bytes + count * (pcm_stride + 4) bytes cross the link.
+ * The dense buffers (4 * capacity * (pcm_stride + 5) bytes of device memory and two small tables) are allocated by the bank's first
+ * open read and freed with the bank; a bank that never calls these runs and allocates exactly what it did without them. */
+/* rows of the open channels of [ch0, ch0+n) of the block last demodulated on `slot`, dense and in ascending channel order:
+   pcm   max_rows * pcm_stride bytes, index   max_rows ints (absolute channel numbers), flags   n bytes (every channel's, as
+   chz_bank_read_pcm_flags_async gives them; may be NULL).  Host buffers must stay valid until the wait below.  max_rows = 0 asks
+   for count and flags only.  Refused (-1, nothing enqueued): a slot whose last open read has not been waited for. */
+int chz_bank_read_pcm_open_async(chz_engine *e, int bank, int slot, int ch0, int n, void *pcm, int *index, unsigned char *flags, int max_rows);
+/* returns once they have landed; *count = open channels found (may exceed max_rows: then the first max_rows are delivered and
+   the slot's image is intact for chz_bank_read_pcm_flags_async).  Refused (-1): no open read outstanding on the slot.
+   Nothing reaches the host buffers before this call: chz_bank_pcm_wait on the slot only waits for the open read's kernels. */
+int chz_bank_pcm_open_wait(chz_engine *e, int bank, int slot, int *count);
+/* the two kernels' own times (ms, from the dispatch packets) of the slot's latest open read, after its wait.  Off until asked for:
+   the first call on a bank turns the timing of its later open reads on; that call, and a call on a slot not timed yet, return 1 */
+int chz_bank_pcm_open_times(chz_engine *e, int bank, int slot, double *count_ms, double *rows_ms);
 
 /* ---- filter2 resident on the device: the channel's private second filter of downconvert() (src/radio.c:1503-1513, created at
  * :1572-1594; presets cwu / cwl with filter2 = 4, isb with filter2 = 1, share/presets.conf:204,223,297) as a stage of the block pipeline.

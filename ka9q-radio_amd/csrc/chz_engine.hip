@@ -164,6 +164,21 @@ struct Bank {
   MiniParams f2_m{}; ChanDesc f2_d{};
   // edits (responses, ISB flags) travel through a pinned staging buffer onto the demodulator stream: in stream order, no drain
   char* f2_stage = nullptr; size_t f2_stage_bytes = 0; hipEvent_t f2_stage_ev = nullptr; bool f2_stage_busy = false;
+  // the open channels' PCM rows, dense (chz_bank_read_pcm_open_async; kernels pcm_open_count / pcm_open_rows on the copy stream):
+  // allocated by the bank's first open read, freed with the bank.  One dense image per slot: a slot's image is written by the kernels of
+  // its read and read by the copies of that read's wait, and a slot takes no second open read before the wait
+  unsigned char* po_rows = nullptr;               // [ND][cap][pcm_stride]
+  int* po_index = nullptr;                        // [ND][cap] absolute channel numbers
+  unsigned long long* po_mask = nullptr;          // [4 tiles] between the two kernels of one read (the copy stream is in order: one for all slots)
+  int* po_tile = nullptr;                         // [tiles]
+  unsigned char* po_flags = nullptr;              // [ND][cap] the range's flag bytes as the kernels found them, from the range's first channel on
+  int* po_count_h = nullptr;                      // [ND] mapped pinned memory: pcm_open_rows stores the count where the host reads it
+  hipEvent_t ev_open[CHZ_ND] = {nullptr, nullptr, nullptr, nullptr};   // on the copy stream behind the count's arrival
+  bool po_pending[CHZ_ND] = {false, false, false, false};              // an open read waits for its chz_bank_pcm_open_wait
+  void* po_pcm[CHZ_ND] = {}; int* po_idx[CHZ_ND] = {}; unsigned char* po_fl[CHZ_ND] = {};   // its host buffers,
+  int po_n[CHZ_ND] = {0, 0, 0, 0}, po_max[CHZ_ND] = {0, 0, 0, 0};                            // its range's length and max_rows
+  bool po_timing = false, po_timed[CHZ_ND] = {false, false, false, false};                   // chz_bank_pcm_open_times
+  hipEvent_t po_tev[CHZ_ND][4] = {};              // begin / end of the two kernels
 };
 // what the bank's demodulators see as one block: filter2 hands them f2_L samples whenever it fires, numbered by its cycles
 static inline int bank_dm_len(const Bank& b) { return b.f2_B > 0 ? b.f2_L : b.olen; }
@@ -253,6 +268,9 @@ struct chz_engine {
   // chz_bank_read_pcm_flags_async copies on a stream of its own, so that block j's PCM travels to the host while block j+1 is being
   // demodulated (on the in-order demodulator stream the copy and the next kernel would take turns); created on first use
   hipStream_t pcmcopy = nullptr;
+  // the second stage of an open read (chz_bank_pcm_open_wait: as many rows as the count says) travels on a stream of its own: on the
+  // copy stream it would queue behind the NEXT block's read, which waits for that block's demodulators; created by the first open read
+  hipStream_t pcmrows = nullptr;
   Lane lanes[CHZ_MAX_LANES];
   int nlanes = 1;
 #define CHZ_INPUT_MARKS 8
@@ -359,6 +377,14 @@ static void free_bank(Bank& b) {
   if (b.f2_stage) (void)hipHostFree(b.f2_stage);
   if (b.f2_stage_ev) (void)hipEventDestroy(b.f2_stage_ev);
   b.f2_stage = nullptr; b.f2_stage_bytes = 0; b.f2_stage_ev = nullptr; b.f2_stage_busy = false;
+  hipFree(b.po_rows); hipFree(b.po_index); hipFree(b.po_mask); hipFree(b.po_tile); hipFree(b.po_flags);
+  if (b.po_count_h) (void)hipHostFree(b.po_count_h);
+  b.po_rows = nullptr; b.po_index = nullptr; b.po_mask = nullptr; b.po_tile = nullptr; b.po_flags = nullptr; b.po_count_h = nullptr; b.po_timing = false;
+  for (int s = 0; s < CHZ_ND; s++) {
+    if (b.ev_open[s]) (void)hipEventDestroy(b.ev_open[s]);
+    for (auto& ev : b.po_tev[s]) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
+    b.ev_open[s] = nullptr; b.po_pending[s] = false; b.po_timed[s] = false;
+  }
   if (b.bb_done) (void)hipEventDestroy(b.bb_done);
   b.bb_done = nullptr;
   for (int s = 0; s < CHZ_ND; s++) { if (b.ev_bb[s]) (void)hipEventDestroy(b.ev_bb[s]); b.ev_bb[s] = nullptr; b.bb_rec[s] = false; }
@@ -620,6 +646,7 @@ void chz_engine_destroy(chz_engine* e) {
   if (e->upload) hipStreamSynchronize(e->upload);
   if (e->tail) hipStreamSynchronize(e->tail);
   if (e->pcmcopy) hipStreamSynchronize(e->pcmcopy);
+  if (e->pcmrows) hipStreamSynchronize(e->pcmrows);
   if (e->welch_s) hipStreamSynchronize(e->welch_s);
   drop_graph(e);
   welch_free_all(e);
@@ -653,6 +680,7 @@ void chz_engine_destroy(chz_engine* e) {
   if (e->upload) hipStreamDestroy(e->upload);
   if (e->tail) hipStreamDestroy(e->tail);
   if (e->pcmcopy) hipStreamDestroy(e->pcmcopy);
+  if (e->pcmrows) hipStreamDestroy(e->pcmrows);
   if (e->welch_s) hipStreamDestroy(e->welch_s);
   if (e->welch_in) hipEventDestroy(e->welch_in);
   if (e->welch_done) hipEventDestroy(e->welch_done);
@@ -700,6 +728,7 @@ static int sync_all(chz_engine* e) {
   for (int i = 0; i < e->nlanes; i++) HIPOK(hipStreamSynchronize(e->lanes[i].s));
   if (e->tail) HIPOK(hipStreamSynchronize(e->tail));
   if (e->pcmcopy) HIPOK(hipStreamSynchronize(e->pcmcopy));
+  if (e->pcmrows) HIPOK(hipStreamSynchronize(e->pcmrows));
   if (e->welch_s) { HIPOK(hipStreamSynchronize(e->welch_s)); e->welch_busy = false; for (auto& b : e->banks) b.bb_busy = 0; }
   // nothing is travelling any more: the demodulator launches that follow (a graph capture among them: an eagerly recorded event is no
   // business of a capture) need not wait for the copy stream's last read of their slot
@@ -1966,6 +1995,110 @@ int chz_bank_pcm_wait(chz_engine* e, int bank, int slot) {
   if (!b.dm_chan) return fail(-1, "bank has no demodulator: call chz_bank_set_demod first");
   HIPOK(hipEventSynchronize(b.ev_pcm[slot]));
   return check_device_errors(e);
+}
+// Only the rows somebody will send: the open channels of [ch0, ch0+n) -- demodulator on, flag byte without NO_SAMPLES, MUTE and PENDING --
+// gathered on the device (pcm_open_count, pcm_open_rows) so that n flag bytes + count * (pcm_stride + 4) bytes cross the link instead of
+// n * (pcm_stride + 1).  Two stages, since the host cannot size the row copy before it knows the count:
+//   _open_async  behind ev_pcmgo[slot] on the copy stream, as chz_bank_read_pcm_flags_async: the two kernels and NOTHING ELSE -- they leave
+//                the range's flag bytes in a per-slot image and store the count straight into mapped pinned memory of the bank's own;
+//                ev_pcm[slot] behind them (the slot's next demodulator launch, read_pcm and chz_bank_pcm_wait see this read as they see
+//                any other), ev_open[slot] for the wait
+//   _open_wait   takes the count, copies the flag bytes and min(count, max_rows) index entries and rows on the rows stream and waits
+// No copy in the first stage, and this is what the measurements asked for (profiles/pcm_open.txt): with the flag bytes and the count
+// copied here, a device-to-host copy enqueued behind block j's demodulators held up every copy submitted after it -- block j-1's rows,
+// which the double-buffered loop asks for next -- until block j had been computed, on whatever stream they travelled (as a copy engine
+// that serves its ring in order would).
+// What keeps the dense image safe: (1) the kernels of every open read run on the one in-order copy stream, (2) the kernels read the
+// slot's PCM image and flags in front of ev_pcm[slot], which the slot's next demodulator launch waits for, (3) the image is per slot
+// and a slot with an open read outstanding takes no second one (refused), so by the time the kernels of the slot's next open read
+// are enqueued the copies of the last one have been waited for.  The slot's own PCM image is only read.
+static int pcm_open_alloc(chz_engine* e, Bank& b) {
+  if (!e->pcmrows) HIPOK(stream_create_masked(&e->pcmrows, true));
+  if (b.po_rows) return 0;
+  const size_t cap = (size_t)b.cap, tiles = (size_t)chz::pcm_open_tiles(b.cap);
+  for (int s = 0; s < CHZ_ND; s++) if (!b.ev_open[s]) HIPOK(hipEventCreateWithFlags(&b.ev_open[s], hipEventDisableTiming));
+  if (!b.po_index) HIPOK(hipMalloc((void**)&b.po_index, sizeof(int) * cap * CHZ_ND));
+  if (!b.po_flags) HIPOK(hipMalloc((void**)&b.po_flags, cap * CHZ_ND));
+  if (!b.po_mask) HIPOK(hipMalloc((void**)&b.po_mask, sizeof(unsigned long long) * tiles * (PCMO_TILE / 64)));
+  if (!b.po_tile) HIPOK(hipMalloc((void**)&b.po_tile, sizeof(int) * tiles));
+  if (!b.po_count_h) {
+    HIPOK(hipHostMalloc((void**)&b.po_count_h, sizeof(int) * CHZ_ND, hipHostMallocMapped));
+    for (int s = 0; s < CHZ_ND; s++) b.po_count_h[s] = 0;
+  }
+  HIPOK(hipMalloc((void**)&b.po_rows, (size_t)b.pcm_stride * cap * CHZ_ND));
+  return 0;
+}
+int chz_bank_read_pcm_open_async(chz_engine* e, int bank, int slot, int ch0, int n, void* pcm, int* index, unsigned char* flags, int max_rows) {
+  if (e) { chz_exit::Scope _xd; if (_xd.ok) (void)hipSetDevice(e->device); }       // several engines of one process may sit on different devices (KA9Q_HIP_DEVICES)
+  BANK_CHECK(e, bank, ch0, n);
+  if (slot < 0 || slot >= CHZ_ND) return fail(-1, "bad slot");
+  Bank& b = e->banks[(size_t)bank];
+  if (!b.dm_chan) return fail(-1, "bank has no demodulator: call chz_bank_set_demod first");
+  if (max_rows < 0) return fail(-1, "max_rows must not be negative");
+  if (max_rows > 0 && (!pcm || !index)) return fail(-1, "null argument");
+  if (b.po_pending[slot]) return fail(-1, "slot %d has an open read outstanding: call chz_bank_pcm_open_wait first", slot);
+  { int r = pcm_open_alloc(e, b); if (r) return r; }
+  const size_t so = (size_t)slot * b.cap, stride = (size_t)b.pcm_stride;
+  if (!e->pcmcopy) HIPOK(stream_create_masked(&e->pcmcopy, true));
+  HIPOK(hipEventRecord(b.ev_pcmgo[slot], e->tail));                 // behind the slot's demodulator kernel (and whatever else is queued there)
+  HIPOK(hipStreamWaitEvent(e->pcmcopy, b.ev_pcmgo[slot], 0));
+  b.po_timed[slot] = false;
+  if (n > 0) {
+    chz::PcmOpenParams q{};
+    q.chan = b.dm_chan; q.flags = b.dm_flags + so; q.pcm = b.dm_pcm + so * stride; q.mask = b.po_mask; q.tile_count = b.po_tile;
+    q.flags_out = b.po_flags + so; q.index = b.po_index + so; q.rows = b.po_rows + so * stride; q.count = b.po_count_h + slot;
+    q.ch0 = ch0; q.n = n; q.pcm_stride = b.pcm_stride;
+    hipEvent_t* tv = b.po_timing ? b.po_tev[slot] : nullptr;
+    chz::launch_pcm_open(e->pcmcopy, q, tv ? tv[0] : nullptr, tv ? tv[1] : nullptr, tv ? tv[2] : nullptr, tv ? tv[3] : nullptr);
+    HIPOK(hipGetLastError());
+    b.po_timed[slot] = tv != nullptr;
+  } else b.po_count_h[slot] = 0;                                    // (no open read of this slot is outstanding: nobody else writes the word)
+  HIPOK(hipEventRecord(b.ev_pcm[slot], e->pcmcopy));
+  HIPOK(hipEventRecord(b.ev_open[slot], e->pcmcopy));
+  b.pcm_copying[slot] = true;
+  b.po_pending[slot] = true; b.po_pcm[slot] = pcm; b.po_idx[slot] = index; b.po_fl[slot] = flags; b.po_n[slot] = n; b.po_max[slot] = max_rows;
+  return 0;
+}
+int chz_bank_pcm_open_wait(chz_engine* e, int bank, int slot, int* count) {
+  if (e) { chz_exit::Scope _xd; if (_xd.ok) (void)hipSetDevice(e->device); }       // several engines of one process may sit on different devices (KA9Q_HIP_DEVICES)
+  BANK_CHECK(e, bank, 0, 0);
+  if (slot < 0 || slot >= CHZ_ND) return fail(-1, "bad slot");
+  Bank& b = e->banks[(size_t)bank];
+  if (!b.dm_chan) return fail(-1, "bank has no demodulator: call chz_bank_set_demod first");
+  if (!b.po_pending[slot]) return fail(-1, "slot %d has no open read outstanding", slot);
+  HIPOK(hipEventSynchronize(b.ev_open[slot]));
+  b.po_pending[slot] = false;
+  const int found = __atomic_load_n(b.po_count_h + slot, __ATOMIC_ACQUIRE), k = found < b.po_max[slot] ? found : b.po_max[slot];
+  const size_t so = (size_t)slot * b.cap, stride = (size_t)b.pcm_stride;
+  const bool fl = b.po_fl[slot] != nullptr && b.po_n[slot] > 0;
+  if (fl) HIPOK(hipMemcpyAsync(b.po_fl[slot], b.po_flags + so, (size_t)b.po_n[slot], hipMemcpyDeviceToHost, e->pcmrows));
+  if (k > 0) {
+    HIPOK(hipMemcpyAsync(b.po_idx[slot], b.po_index + so, sizeof(int) * (size_t)k, hipMemcpyDeviceToHost, e->pcmrows));
+    HIPOK(hipMemcpyAsync(b.po_pcm[slot], b.po_rows + so * stride, stride * (size_t)k, hipMemcpyDeviceToHost, e->pcmrows));
+  }
+  if (fl || k > 0) HIPOK(hipStreamSynchronize(e->pcmrows));
+  if (count) *count = found;
+  return check_device_errors(e);
+}
+// the two kernels' own times (ms) of the slot's latest open read, once it has been waited for.  Timing costs every open read two event
+// pairs, so it is off until the first call on a bank turns it on: that call and any call on a slot not yet timed return 1
+int chz_bank_pcm_open_times(chz_engine* e, int bank, int slot, double* count_ms, double* rows_ms) {
+  if (e) { chz_exit::Scope _xd; if (_xd.ok) (void)hipSetDevice(e->device); }
+  BANK_CHECK(e, bank, 0, 0);
+  if (slot < 0 || slot >= CHZ_ND) return fail(-1, "bad slot");
+  Bank& b = e->banks[(size_t)bank];
+  if (!b.dm_chan) return fail(-1, "bank has no demodulator: call chz_bank_set_demod first");
+  if (!b.po_timing) {
+    for (int s = 0; s < CHZ_ND; s++) for (auto& ev : b.po_tev[s]) if (!ev) HIPOK(hipEventCreate(&ev));
+    b.po_timing = true;
+  }
+  if (!b.po_timed[slot] || b.po_pending[slot]) return 1;
+  float c = 0.0f, r = 0.0f;
+  HIPOK(hipEventElapsedTime(&c, b.po_tev[slot][0], b.po_tev[slot][1]));
+  HIPOK(hipEventElapsedTime(&r, b.po_tev[slot][2], b.po_tev[slot][3]));
+  if (count_ms) *count_ms = c;
+  if (rows_ms) *rows_ms = r;
+  return 0;
 }
 int chz_bank_read_pcm(chz_engine* e, int bank, int slot, int ch0, int n, void* pcm, chz_demod_status* status) {
   return read_pcm(e, bank, slot, ch0, n, pcm, status, true);

@@ -3503,6 +3503,96 @@ __global__ void __launch_bounds__(256) f2_ovs(F2Params p) {
 }
 
 // ------------------------------------------------------------------------------
+// The open channels' PCM rows, dense (chz_bank_read_pcm_open_async): of channels [ch0, ch0 + n) of a slot, those whose demodulator
+// is on and whose flag byte says neither "no samples" nor "mute" nor "pending" are the ones send_output() would be handed samples
+// for; their rows are gathered in ascending channel order into a dense image, so that only they cross the host link.
+// Two launches, no atomics, no LDS, no barrier: a TILE of PCMO_TILE = 256 channels belongs to one wavefront (four a workgroup).
+//   pcm_open_count  four ballots a tile: the 64-bit masks of its four groups of 64 channels and their popcount, one int a tile;
+//                   the range's flag bytes go into an image of their own on the way
+//   pcm_open_rows   a tile's first dense row is the sum of the earlier tiles' counts (each lane adds every 64th, a butterfly of
+//                   shuffles adds the lanes: 81 loads a lane for 1.3 M channels, all of them L2 hits); inside a group the lane of
+//                   channel c writes index[base + popcount(mask below c)], and lane r finds the r-th set bit of the mask -- the
+//                   group's r-th open channel -- by halving (six popcounts).  The group's open rows then move as ONE flat run of
+//                   words: word w of the run is word w % wpr of row w / wpr, consecutive lanes take consecutive words, so every
+//                   store instruction writes 64 consecutive words of the dense image and every load reads whole rows front to
+//                   back.  (row, word) advance by 64 words per turn with one compare, not a division; the source lane of a row
+//                   comes from a shuffle, whose trip count is the same in every lane.
+// The word is the widest the rows allow (launch_pcm_open: 16, 8 or 4 bytes from the stride and the two images' addresses).
+// Same input, same bytes: nothing here depends on the order in which waves run.
+// ------------------------------------------------------------------------------
+#define PCMO_TILE 256
+#define PCMO_CLOSED_BITS (1 | 2 | CHZ_FLAG_PENDING_BIT)      // CHZ_FLAG_NO_SAMPLES | CHZ_FLAG_MUTE | CHZ_FLAG_PENDING
+struct alignas(16) PcmWord16 { unsigned a, b, c, d; };
+struct alignas(8) PcmWord8 { unsigned a, b; };
+struct PcmOpenParams {
+  const DemodChan* chan;             // [cap]
+  const unsigned char* flags;        // [cap] this slot
+  const unsigned char* pcm;          // [cap][pcm_stride] this slot
+  unsigned long long* mask;          // [4 * tiles] the open channels of each group of 64, bit l = channel ch0 + 64 group + l
+  int* tile_count;                   // [tiles]
+  unsigned char* flags_out;          // [n] the range's flag bytes, from ch0 on: what the host is handed, whatever the slot holds by then
+  int* index;                        // [n] dense: absolute channel numbers
+  unsigned char* rows;               // [n][pcm_stride] dense
+  int* count;                        // the open channels of the range (the engine points this at mapped host memory)
+  int ch0, n, pcm_stride, tiles;
+};
+__global__ void __launch_bounds__(256) pcm_open_count(PcmOpenParams p) {
+  const int lane = threadIdx.x & 63;
+  const int tile = (int)blockIdx.x * ((int)blockDim.x >> 6) + ((int)threadIdx.x >> 6);
+  if (tile >= p.tiles) return;                               // wave-uniform
+  int c = 0;
+  for (int g = 0; g < PCMO_TILE / 64; g++) {
+    const int i = tile * PCMO_TILE + g * 64 + lane;
+    bool open = false;
+    if (i < p.n) {
+      const unsigned char f = p.flags[p.ch0 + i];
+      p.flags_out[i] = f;                                    // every channel's, demodulator or not, as read_pcm_flags gives them
+      open = p.chan[p.ch0 + i].on != 0 && (f & PCMO_CLOSED_BITS) == 0;
+    }
+    const unsigned long long m = __ballot(open);
+    if (lane == 0) p.mask[tile * (PCMO_TILE / 64) + g] = m;
+    c += __popcll(m);
+  }
+  if (lane == 0) p.tile_count[tile] = c;
+}
+template <class W>
+__global__ void __launch_bounds__(256) pcm_open_rows(PcmOpenParams p) {
+  const int lane = threadIdx.x & 63;
+  const int tile = (int)blockIdx.x * ((int)blockDim.x >> 6) + ((int)threadIdx.x >> 6);
+  if (tile >= p.tiles) return;                               // wave-uniform
+  int base = 0;
+  for (int t = lane; t < tile; t += 64) base += p.tile_count[t];
+  for (int d = 32; d > 0; d >>= 1) base += __shfl_xor(base, d);
+  const int wpr = p.pcm_stride / (int)sizeof(W);             // words a row
+  const int q64 = 64 / wpr, r64 = 64 - q64 * wpr;            // 64 words further: q64 rows and r64 words
+  for (int g = 0; g < PCMO_TILE / 64; g++) {
+    const unsigned long long m = p.mask[tile * (PCMO_TILE / 64) + g];
+    const int cnt = __popcll(m);
+    const int first = tile * PCMO_TILE + g * 64;             // the group's first channel, counted from ch0
+    if ((m >> lane) & 1ull) p.index[base + __popcll(m & ((1ull << lane) - 1ull))] = p.ch0 + first + lane;
+    // lane r: which lane's channel is the group's r-th open one (meaningful for r < cnt)
+    int sel = 0;
+    { unsigned long long v = m; int r = lane;
+      for (int h = 32; h > 0; h >>= 1) {
+        const int below = __popcll(v & ((1ull << h) - 1ull));
+        if (r >= below) { r -= below; v >>= h; sel += h; }
+      } }
+    const W* __restrict__ src = reinterpret_cast<const W*>(p.pcm + (size_t)(p.ch0 + first) * (size_t)p.pcm_stride);
+    W* __restrict__ dst = reinterpret_cast<W*>(p.rows + (size_t)base * (size_t)p.pcm_stride);
+    const int total = cnt * wpr;                             // at most 64 rows of at most 8 * 10240 bytes
+    int r = lane / wpr, k = lane - r * wpr;
+    for (int w0 = 0; w0 < total; w0 += 64) {
+      const int from = __shfl(sel, r & 63);
+      if (w0 + lane < total) dst[w0 + lane] = src[(size_t)from * (size_t)wpr + k];
+      r += q64; k += r64;
+      if (k >= wpr) { k -= wpr; r++; }
+    }
+    base += cnt;
+  }
+  if (tile == p.tiles - 1 && lane == 0) *p.count = base;
+}
+
+// ------------------------------------------------------------------------------
 // Small REAL inline masters with decimating slaves (wfm's composite master, src/wfm.c:70-89: L 7680, M 7681 with a REAL
 // and two COMPLEX slaves of olen 960; stereod, rdsd, packetd and ctcss keep the like).  One workgroup per request,
 // everything in LDS, stateless like mini_ovs: a request carries its whole N-sample REAL window.

@@ -275,6 +275,18 @@ inline void launch_f2(hipStream_t s, const F2Params& p, int nch, hipEvent_t e0 =
   const int threads = N / 4 >= 256 ? 256 : (N / 4 >= 64 ? (N / 4 + 63) / 64 * 64 : 64);
   CHZ_LAUNCH(f2_ovs, nch, threads, f2_lds_bytes(N), s, e0, e1, p);
 }
+// the open channels' rows of p.n >= 1 channels, dense: count, then scatter with the widest word the stride and both images' addresses
+// allow (strides are multiples of 4).  The event pairs time the two kernels (scripts/pcm_open_probe.py).
+inline int pcm_open_tiles(int n) { return (n + PCMO_TILE - 1) / PCMO_TILE; }
+inline void launch_pcm_open(hipStream_t s, PcmOpenParams p, hipEvent_t c0 = nullptr, hipEvent_t c1 = nullptr, hipEvent_t r0 = nullptr, hipEvent_t r1 = nullptr) {
+  p.tiles = pcm_open_tiles(p.n);
+  const int grid = (p.tiles + 3) / 4;
+  const size_t a = (size_t)reinterpret_cast<uintptr_t>(p.pcm) | (size_t)reinterpret_cast<uintptr_t>(p.rows) | (size_t)p.pcm_stride;
+  CHZ_LAUNCH(pcm_open_count, grid, 256, 0, s, c0, c1, p);
+  if ((a & 15) == 0) CHZ_LAUNCH(pcm_open_rows<PcmWord16>, grid, 256, 0, s, r0, r1, p);
+  else if ((a & 7) == 0) CHZ_LAUNCH(pcm_open_rows<PcmWord8>, grid, 256, 0, s, r0, r1, p);
+  else CHZ_LAUNCH(pcm_open_rows<unsigned>, grid, 256, 0, s, r0, r1, p);
+}
 // host side of the coherent modes and the PL-tone squelch: what init_pll() (src/osc.c:130-136, called once when the demodulator
 // starts, src/linear.c:41) and the tone set-up of demod_fm() (src/fm.c:50-61) leave behind
 inline DemodExt demod_ext_init() {

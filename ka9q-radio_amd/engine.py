@@ -89,7 +89,8 @@ SYMBOLS = [
     "chz_bank_create", "chz_bank_create_shared", "chz_bank_set_rows", "chz_bank_set_row_responses", "chz_bank_set_responses", "chz_bank_set_shifts", "chz_bank_set_active",
     "chz_bank_execute", "chz_bank_execute_range", "chz_bank_destroy", "chz_bank_read", "chz_bank_read_async",
     "chz_spectrum_read_async", "chz_host_callback", "chz_host_alloc", "chz_host_free", "chz_host_register", "chz_host_unregister",
-    "chz_bank_output_device", "chz_bank_write_block", "chz_bank_demod", "chz_bank_demod_auto", "chz_bank_read_pcm_flags_async", "chz_bank_pcm_wait", "chz_step", "chz_run_blocks", "chz_gather_descriptor",
+    "chz_bank_output_device", "chz_bank_write_block", "chz_bank_demod", "chz_bank_demod_auto", "chz_bank_read_pcm_flags_async", "chz_bank_pcm_wait",
+    "chz_bank_read_pcm_open_async", "chz_bank_pcm_open_wait", "chz_bank_pcm_open_times", "chz_step", "chz_run_blocks", "chz_gather_descriptor",
     "chz_bank_set_tuning", "chz_bank_read_power", "chz_bank_read_power_async",
     "chz_input_write_i16", "chz_input_write_i16_device", "chz_input_stats",
     "chz_bank_enable_noise", "chz_bank_read_noise", "chz_bank_read_noise_async", "chz_bank_create_real", "chz_bank_set_isb", "chz_bank_set_beam",
@@ -564,6 +565,25 @@ class Bank:
         _check(L.chz_bank_read_pcm_flags_async(self.eng._h, self.id, slot, ch0, n, pcm.ctypes.data, fl.ctypes.data))
         self.eng.sync()
         return pcm, fl
+
+    def read_pcm_open(self, slot, ch0=0, n=None, max_rows=None):
+        """(count, index int32[k], pcm uint8[k][stride], flags uint8[n]), k = min(count, max_rows): the rows of the open channels of
+        [ch0, ch0+n) only -- demodulator on, flag byte without NO_SAMPLES, MUTE and PENDING -- dense and in ascending channel order
+        (chz_bank_read_pcm_open_async + chz_bank_pcm_open_wait).  max_rows defaults to n."""
+        if n is None:
+            n = self.active - ch0
+        if max_rows is None:
+            max_rows = n
+        stride = _check(lib().chz_bank_pcm_stride(self.eng._h, self.id))
+        pcm = np.zeros((max(max_rows, 0), stride), np.uint8); idx = np.zeros(max(max_rows, 0), np.int32); fl = np.zeros(max(n, 0), np.uint8)
+        cnt = C.c_int(0)
+        L = lib()
+        L.chz_bank_read_pcm_open_async.argtypes = [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i]
+        L.chz_bank_pcm_open_wait.argtypes = [_vp, _i, _i, C.POINTER(C.c_int)]
+        _check(L.chz_bank_read_pcm_open_async(self.eng._h, self.id, slot, ch0, n, pcm.ctypes.data, idx.ctypes.data, fl.ctypes.data, max_rows))
+        _check(L.chz_bank_pcm_open_wait(self.eng._h, self.id, slot, C.byref(cnt)))
+        k = min(cnt.value, max_rows)
+        return cnt.value, idx[:k], pcm[:k], fl
 
     def enable_noise(self, samprate):
         """estimate_noise() (src/radio.c:1783-1866) on the device after every block; samprate = front-end rate in Hz."""
