@@ -99,6 +99,35 @@ int chz_input_write_i16_device(chz_engine *e, const short *dev_samples, long n, 
 /* sum of x*x and count of |x| > 32766 over the L new samples of the block last transformed into `slot`
  * (what rx_callback accumulates into frontend->if_power / overranges, src/rx888.c:780-795); synchronous */
 int chz_input_stats(chz_engine *e, int slot, unsigned long long *energy, unsigned *clips);
+/* The other front ends' raw A/D formats: replaces the per-sample conversion loops of airspy.c:412-427 + airspy-unpack.c, the switch of
+ * hydrasdr.c:660-833 and rtlsdr.c:323-339.  The raw bytes cross the link (1.5 bytes a sample PACKED12, 2 a complex sample 8-bit I/Q) into
+ * a device staging buffer -- allocated by an engine's first raw write, freed with the engine -- and the raw_unpack kernel converts them
+ * into the FLOAT input ring at the write position, so everything behind the ring is what it is for chz_input_write, and the two may
+ * alternate on one engine.  (An engine in int16 mode, chz_input_write_i16, refuses raw writes, and the other way round.)
+ *   n        samples; complex samples for the I/Q formats.  PACKED12: a multiple of 8
+ *   bits     CHZ_RAW_U16 only, 2..16: frontend->bitspersample
+ *   scale    sdr->scale.  x -> (float)(scale * x), the product in double; PACKED12 -> (float)scale * (float)x, the product in float, as
+ *            airspy_unpack() does, which is handed (float)sdr->scale
+ *   ticket   out (may be NULL): this write's number, counted per engine from 0; the statistics of the last CHZ_RAW_TICKETS writes can be read
+ * chz_input_raw_stats: the exact sum of x*x (x*x + y*y) over the write, the samples the reference counts into frontend->overranges (PACKED12
+ * x == 2047 || x <= -2047; U16 x >= offset-1 || x <= -offset; 16-bit >= 32767 || <= -32768; 8-bit >= 127 || <= -128; an I/Q sample once if
+ * either component clips) and the clipped components one by one (what rtlsdr.c:324-334 adds up; == clipped_samples for REAL formats).
+ * Synchronous on the engine's stream, like chz_input_stats.  Any of the three pointers may be NULL.
+ * The _device form reads the caller's device buffer in place: 16-byte aligned, and readable up to the next 16-byte boundary behind the
+ * last sample (the kernel loads whole 8- or 16-byte groups and masks what lies beyond n). */
+#define CHZ_RAW_PACKED12 0   /* REAL: 8 samples in 3 little-endian 32-bit words, offset 2048 (airspy-unpack.c; hydrasdr RAW) */
+#define CHZ_RAW_U16      1   /* REAL: uint16, offset 1 << (bits-1)      (hydrasdr.c:681-698) */
+#define CHZ_RAW_S16      2   /* REAL: int16                             (:700-715) */
+#define CHZ_RAW_U8       3   /* REAL: uint8, offset 128                 (:759-774) */
+#define CHZ_RAW_S8       4   /* REAL: int8                              (:776-791) */
+#define CHZ_RAW_S16_IQ   5   /* COMPLEX: int16 I,Q                      (:729-746) */
+#define CHZ_RAW_U8_IQ    6   /* COMPLEX: uint8 I,Q, offset 128          (:793-810; rtlsdr.c:323-339) */
+#define CHZ_RAW_S8_IQ    7   /* COMPLEX: int8 I,Q                       (:812-829) */
+#define CHZ_RAW_TICKETS  8   /* the statistics of this many latest raw writes stay readable */
+int chz_input_raw_check(int in_type, int format, int bits, long n);   /* 0, or < 0 and chz_last_error(); touches no device */
+int chz_input_write_raw(chz_engine *e, int format, int bits, const void *host_samples, long n, double scale, unsigned *ticket);
+int chz_input_write_raw_device(chz_engine *e, int format, int bits, const void *dev_samples, long n, double scale, unsigned *ticket);
+int chz_input_raw_stats(chz_engine *e, unsigned ticket, unsigned long long *energy, unsigned *clipped_samples, unsigned *clipped_components);
 /* direct access to the device ring for HBM-resident benchmarks */
 int chz_input_ring(chz_engine *e, float **dev_ring, long *ring_len_floats);
 /* Re-seat the input ring in front of block `job`: the next L samples written are that block's new samples and `history`

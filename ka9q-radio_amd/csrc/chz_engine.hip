@@ -281,6 +281,10 @@ struct chz_engine {
   // raw A/D input: the ring holds int16 and fwd_first_real converts on load
   short* ring16 = nullptr; float scale16 = 1.0f; int derand = 0;
   unsigned long long* energy_part = nullptr; unsigned* clip_part = nullptr; int stat_n = 0;   // [ND][stat_n] per-wave partials
+  // the other raw A/D formats (chz_input_write_raw): staged raw bytes, converted INTO the float ring by raw_unpack; all made by the first raw write
+  void* raw_stage = nullptr;                  // a whole ring of the widest format (2 bytes a float) + 16 bytes of slack
+  RawPart* raw_part = nullptr;                // [CHZ_RAW_TICKETS][CHZ_RAW_MAX_GRID] per-workgroup statistics of the latest writes
+  unsigned raw_tickets = 0; int raw_grid[CHZ_RAW_TICKETS] = {};   // writes so far; workgroups of the write in each ticket slot (0: an empty write)
   long wpos = 0;                              // write position (floats)
   float2* spec[CHZ_ND] = {nullptr, nullptr, nullptr, nullptr};
   bool spec_owned[CHZ_ND] = {false, false, false, false};
@@ -665,7 +669,7 @@ void chz_engine_destroy(chz_engine* e) {
   if (e->ev_end_tail) hipEventDestroy(e->ev_end_tail);
   for (auto ev : e->notch_ev) if (ev) hipEventDestroy(ev);
   for (auto& b : e->banks) free_bank(b);
-  hipFree(e->ring); hipFree(e->ring16); hipFree(e->energy_part); hipFree(e->clip_part);
+  hipFree(e->ring); hipFree(e->ring16); hipFree(e->energy_part); hipFree(e->clip_part); hipFree(e->raw_stage); hipFree(e->raw_part);
   for (int i = 0; i < CHZ_ND; i++) if (e->spec_owned[i]) hipFree(e->spec[i]);
   for (int i = 0; i < CHZ_ND; i++) if (e->energy[i]) hipFree(e->energy[i]);
   if (e->blue) {
@@ -775,7 +779,7 @@ static int ring16_write(chz_engine* e, const short* src, long n, float scale, in
   if (n < 0 || n > e->ring_len) return fail(-1, "write of %ld samples does not fit the ring", n);
   HIPOK(hipSetDevice(e->device));
   if (!e->ring16) {
-    if (e->wpos != (long)(e->M - 1)) return fail(-1, "int16 and float input cannot be mixed on one engine");
+    if (e->wpos != (long)(e->M - 1) || e->raw_tickets) return fail(-1, "int16 and float input cannot be mixed on one engine");
     HIPOK(hipMalloc((void**)&e->ring16, sizeof(short) * (size_t)e->ring_len));
     HIPOK(hipMemset(e->ring16, 0, sizeof(short) * (size_t)e->ring_len));
     e->stat_n = e->blue ? blue_grid(e->blue->Mz) * 4 : e->plan.grid1 * (e->plan.block1 / 64);     // per-wave partials of the pass that loads the samples
@@ -818,6 +822,81 @@ int chz_input_stats(chz_engine* e, int slot, unsigned long long* energy, unsigne
   for (size_t i = 0; i < en.size(); i++) { se += en[i]; sc += cl[i]; }
   if (energy) *energy = se;
   if (clips) *clips = sc;
+  return 0;
+}
+// The other front ends' raw formats (airspy.c:412-427 + airspy-unpack.c, hydrasdr.c:660-833, rtlsdr.c:323-339): the raw bytes are staged
+// on the device and raw_unpack converts them into the FLOAT ring, so nothing behind the ring knows the difference.
+static_assert(CHZ_RAW_PACKED12 == RAW_PACKED12 && CHZ_RAW_U16 == RAW_U16 && CHZ_RAW_S16 == RAW_S16 && CHZ_RAW_U8 == RAW_U8 && CHZ_RAW_S8 == RAW_S8 &&
+              CHZ_RAW_S16_IQ == RAW_S16_IQ && CHZ_RAW_U8_IQ == RAW_U8_IQ && CHZ_RAW_S8_IQ == RAW_S8_IQ, "chz_engine.h and chz_kernels.h number the raw formats alike");
+int chz_input_raw_check(int in_type, int format, int bits, long n) {
+  if (format < 0 || format >= RAW_FORMATS) return fail(-1, "unknown raw sample format %d", format);
+  if (in_type != CHZ_REAL && in_type != CHZ_COMPLEX) return fail(-1, "unknown input type %d", in_type);
+  if (raw_is_iq(format) != (in_type == CHZ_COMPLEX))
+    return fail(-1, "raw format %d holds %s samples, the master is %s", format, raw_is_iq(format) ? "I/Q" : "real", in_type == CHZ_COMPLEX ? "COMPLEX" : "REAL");
+  if (n < 0) return fail(-1, "write of %ld samples", n);
+  if (format == RAW_PACKED12 && n % 8 != 0) return fail(-1, "packed 12-bit samples come in groups of 8 (n = %ld)", n);
+  if (format == RAW_U16 && (bits < 2 || bits > 16)) return fail(-1, "uint16 samples of %d bits (2..16)", bits);
+  return 0;
+}
+static size_t raw_bytes(int format, long n) {
+  switch (format) {
+    case RAW_PACKED12: return (size_t)n / 8 * 12;
+    case RAW_S16_IQ: return (size_t)n * 4;
+    case RAW_U16: case RAW_S16: case RAW_U8_IQ: case RAW_S8_IQ: return (size_t)n * 2;
+    default: return (size_t)n;
+  }
+}
+static int raw_write(chz_engine* e, int format, int bits, const void* src, long n, double scale, unsigned* ticket, bool on_device) {
+  if (!e || !src) return fail(-1, "null argument");
+  { int r = chz_input_raw_check(e->in_type, format, bits, n); if (r) return r; }
+  if (e->ring16) return fail(-1, "int16 and raw-format input cannot be mixed on one engine");
+  if (n > e->ring_len / e->per) return fail(-1, "write of %ld samples does not fit the ring", n);
+  const long nf = n * e->per;
+  if (on_device && (reinterpret_cast<uintptr_t>(src) & 15) != 0) return fail(-1, "raw samples in device memory must be 16-byte aligned");
+  HIPOK(hipSetDevice(e->device));
+  if (!e->raw_part) HIPOK(hipMalloc((void**)&e->raw_part, sizeof(RawPart) * (size_t)CHZ_RAW_TICKETS * CHZ_RAW_MAX_GRID));
+  if (!on_device && !e->raw_stage) HIPOK(hipMalloc(&e->raw_stage, 2 * (size_t)e->ring_len + 16));
+  const int slot = (int)(e->raw_tickets % CHZ_RAW_TICKETS);      // still the slot of a readable ticket until this write has been issued
+  int grid = 0;
+  if (nf > 0) {
+    { int r = welch_guard(e, e->wpos / e->per, n); if (r) return r; }
+    if (!on_device) HIPOK(hipMemcpyAsync(e->raw_stage, src, raw_bytes(format, n), hipMemcpyHostToDevice, e->stream));
+    RawUnpackParams p{};
+    p.src = on_device ? src : e->raw_stage; p.ring = e->ring; p.ring_len = e->ring_len; p.wpos = e->wpos; p.nf = nf;
+    p.scale = scale; p.scalef = (float)scale; p.offset = format == RAW_U16 ? 1 << (bits - 1) : 0;
+    p.part = e->raw_part + (size_t)slot * CHZ_RAW_MAX_GRID;
+    if (launch_raw_unpack(format, e->stream, p)) return fail(-1, "unknown raw sample format %d", format);
+    grid = raw_unpack_grid(nf);
+    e->wpos = (e->wpos + nf) % e->ring_len;
+    if (e->nlanes > 1) { HIPOK(hipEventRecord(e->input_ready, e->stream)); e->input_pending = true; }
+  }
+  e->raw_grid[slot] = grid;
+  if (ticket) *ticket = e->raw_tickets;
+  e->raw_tickets++;
+  return 0;
+}
+int chz_input_write_raw(chz_engine* e, int format, int bits, const void* host, long n, double scale, unsigned* ticket) {
+  return raw_write(e, format, bits, host, n, scale, ticket, false);
+}
+int chz_input_write_raw_device(chz_engine* e, int format, int bits, const void* dev, long n, double scale, unsigned* ticket) {
+  return raw_write(e, format, bits, dev, n, scale, ticket, true);
+}
+int chz_input_raw_stats(chz_engine* e, unsigned ticket, unsigned long long* energy, unsigned* clipped_samples, unsigned* clipped_components) {
+  if (!e) return fail(-1, "null engine");
+  if (ticket >= e->raw_tickets) return fail(-1, "raw write %u has not been issued (%u so far)", ticket, e->raw_tickets);
+  if (e->raw_tickets - ticket > CHZ_RAW_TICKETS) return fail(-1, "the statistics of raw write %u are gone: the last %d of %u are kept", ticket, CHZ_RAW_TICKETS, e->raw_tickets);
+  HIPOK(hipSetDevice(e->device));
+  const int slot = (int)(ticket % CHZ_RAW_TICKETS);
+  std::vector<RawPart> part((size_t)e->raw_grid[slot]);
+  if (!part.empty()) {
+    HIPOK(hipMemcpyAsync(part.data(), e->raw_part + (size_t)slot * CHZ_RAW_MAX_GRID, sizeof(RawPart) * part.size(), hipMemcpyDeviceToHost, e->stream));
+    HIPOK(hipStreamSynchronize(e->stream));
+  }
+  unsigned long long se = 0; unsigned cs = 0, cc = 0;
+  for (const RawPart& q : part) { se += q.energy; cs += q.clipped_samples; cc += q.clipped_components; }
+  if (energy) *energy = se;
+  if (clipped_samples) *clipped_samples = cs;
+  if (clipped_components) *clipped_components = cc;
   return 0;
 }
 int chz_input_seek(chz_engine* e, unsigned job, const float* history) {

@@ -4589,4 +4589,114 @@ __global__ void __launch_bounds__(256) bb_ring_append(BbAppendParams q) {
   }
 }
 
+// ------------------------------------------------------------------------------
+// raw_unpack: the raw A/D formats of the front ends other than the RX888 (chz_input_write_raw: airspy-unpack.c, the switch of
+// hydrasdr.c:660-833, rtlsdr.c:323-339) converted from a staging buffer into the FLOAT input ring at the write position, with the
+// reference's energy sum and overrange counts on the way.  One instantiation per format (the numbers are CHZ_RAW_* of chz_engine.h).
+//   A thread owns 8 consecutive ring floats (8 REAL samples or 4 I/Q pairs) and loads their source in one access: three dwords
+//   (PACKED12), 16 bytes (the 16-bit formats), 8 bytes (the 8-bit ones).  The last group's load may reach past the samples (the
+//   staging buffer has 16 bytes of slack; an aligned load never leaves the 16 bytes it starts in): what lies at or beyond nf is
+//   masked out of stores and statistics.
+//   Stores: two float4 where the group is whole, does not straddle the ring end and starts 4-float aligned -- `aligned` says so for
+//   the positions in front of the ring end (bit 0: wpos % 4 == 0) and behind it (bit 1: (wpos - ring_len) % 4 == 0), the same for
+//   every group of a launch since a group advances 8 floats; scalar stores with the wrap elsewhere.
+//   Statistics: per thread over its grid-stride loop, per wavefront by shuffle, one partial per workgroup through LDS, stored
+//   with an ordinary store into part[workgroup]; the host adds the partials (chz_input_raw_stats).  Integer sums: no order, no atomics.
+// ------------------------------------------------------------------------------
+enum { RAW_PACKED12 = 0, RAW_U16 = 1, RAW_S16 = 2, RAW_U8 = 3, RAW_S8 = 4, RAW_S16_IQ = 5, RAW_U8_IQ = 6, RAW_S8_IQ = 7, RAW_FORMATS = 8 };
+#define CHZ_RAW_MAX_GRID 2048
+struct alignas(16) RawPart { unsigned long long energy; unsigned clipped_samples, clipped_components; };
+struct RawUnpackParams {
+  const void* src;             // raw samples, 16-byte aligned
+  float* ring;                 // [ring_len]
+  long ring_len, wpos, nf;     // floats: the ring, where the first one goes (< ring_len), how many (<= ring_len)
+  double scale; float scalef;  // sdr->scale and (float)sdr->scale (PACKED12)
+  int offset;                  // RAW_U16: 1 << (bits - 1)
+  int aligned;                 // bit 0 / bit 1: see above
+  RawPart* part;               // [gridDim.x] this write's partials
+};
+constexpr bool raw_is_iq(int F) { return F >= RAW_S16_IQ; }
+// the group's 8 integer codes, offset removed
+template <int F> __device__ __forceinline__ void raw_load8(const RawUnpackParams& p, long g, int x[8]) {
+  if constexpr (F == RAW_PACKED12) {
+    const unsigned* __restrict__ up = static_cast<const unsigned*>(p.src) + 3 * g;
+    const unsigned w0 = up[0], w1 = up[1], w2 = up[2];
+    const unsigned s[8] = {w0 >> 20, w0 >> 8, (w0 << 4) | (w1 >> 28), w1 >> 16, w1 >> 4, (w1 << 8) | (w2 >> 24), w2 >> 12, w2};
+#pragma unroll
+    for (int j = 0; j < 8; j++) x[j] = (int)(s[j] & 0xfffu) - 2048;
+  } else if constexpr (F == RAW_U16 || F == RAW_S16 || F == RAW_S16_IQ) {
+    const PcmWord16 v = static_cast<const PcmWord16*>(p.src)[g];
+    const unsigned w[4] = {v.a, v.b, v.c, v.d};
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      if constexpr (F == RAW_U16) { x[2 * k] = (int)(w[k] & 0xffffu) - p.offset; x[2 * k + 1] = (int)(w[k] >> 16) - p.offset; }
+      else { x[2 * k] = (int)(short)(w[k] & 0xffffu); x[2 * k + 1] = (int)(short)(w[k] >> 16); }
+    }
+  } else {
+    const PcmWord8 v = static_cast<const PcmWord8*>(p.src)[g];
+    const unsigned w[2] = {v.a, v.b};
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const unsigned b = (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
+      if constexpr (F == RAW_U8 || F == RAW_U8_IQ) x[j] = (int)b - 128;
+      else x[j] = (int)(signed char)b;
+    }
+  }
+}
+template <int F> __device__ __forceinline__ bool raw_clipped(const RawUnpackParams& p, int x) {
+  if constexpr (F == RAW_PACKED12) return x == 2047 || x <= -2047;
+  else if constexpr (F == RAW_U16) return x >= p.offset - 1 || x <= -p.offset;
+  else if constexpr (F == RAW_S16 || F == RAW_S16_IQ) return x >= 32767 || x <= -32768;
+  else return x >= 127 || x <= -128;
+}
+template <int F>
+__global__ void __launch_bounds__(256) raw_unpack(RawUnpackParams p) {
+  __shared__ unsigned long long red[2][4];
+  const long groups = (p.nf + 7) >> 3;
+  unsigned long long energy = 0, clips = 0;            // clips: samples in the low word, components in the high one
+  for (long g = (long)blockIdx.x * 256 + (long)threadIdx.x; g < groups; g += (long)gridDim.x * 256) {
+    int x[8]; float f[8];
+    raw_load8<F>(p, g, x);
+    const long c0 = 8 * g;                             // the group's first float, counted from the write position
+    const int valid = p.nf - c0 >= 8 ? 8 : (int)(p.nf - c0);
+    bool cl[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      if constexpr (F == RAW_PACKED12) f[j] = __fmul_rn(p.scalef, (float)x[j]);
+      else f[j] = (float)(p.scale * (double)x[j]);
+      cl[j] = j < valid && raw_clipped<F>(p, x[j]);
+      if (j < valid) energy += (unsigned long long)((long long)x[j] * (long long)x[j]);
+      if (cl[j]) clips += 1ull << 32;
+    }
+    if constexpr (raw_is_iq(F)) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) if (cl[2 * k] || cl[2 * k + 1]) clips += 1ull;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; j++) if (cl[j]) clips += 1ull;
+    }
+    long pos = p.wpos + c0;
+    const bool wrapped = pos >= p.ring_len;
+    if (wrapped) pos -= p.ring_len;
+    if (valid == 8 && pos + 8 <= p.ring_len && ((p.aligned >> (wrapped ? 1 : 0)) & 1)) {
+      float4* __restrict__ d = reinterpret_cast<float4*>(p.ring + pos);
+      d[0] = make_float4(f[0], f[1], f[2], f[3]);
+      d[1] = make_float4(f[4], f[5], f[6], f[7]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; j++)
+        if (j < valid) { long q = pos + j; if (q >= p.ring_len) q -= p.ring_len; p.ring[q] = f[j]; }
+    }
+  }
+  for (int d = 32; d > 0; d >>= 1) { energy += __shfl_xor(energy, d); clips += __shfl_xor(clips, d); }
+  const int wave = (int)threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { red[0][wave] = energy; red[1][wave] = clips; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned long long e = red[0][0] + red[0][1] + red[0][2] + red[0][3], c = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    RawPart r; r.energy = e; r.clipped_samples = (unsigned)c; r.clipped_components = (unsigned)(c >> 32);
+    p.part[blockIdx.x] = r;
+  }
+}
+
 }  // namespace chz

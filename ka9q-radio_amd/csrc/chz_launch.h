@@ -287,6 +287,20 @@ inline void launch_pcm_open(hipStream_t s, PcmOpenParams p, hipEvent_t c0 = null
   else if ((a & 7) == 0) CHZ_LAUNCH(pcm_open_rows<PcmWord8>, grid, 256, 0, s, r0, r1, p);
   else CHZ_LAUNCH(pcm_open_rows<unsigned>, grid, 256, 0, s, r0, r1, p);
 }
+// raw A/D formats into the float ring: a capped grid of 256-thread workgroups, each thread 8 floats a turn.  p.part must hold
+// raw_unpack_grid(p.nf) partials; p.aligned is filled in here.  -1: no such format.
+inline int raw_unpack_grid(long nf) {
+  const long wg = ((nf + 7) / 8 + 255) / 256;
+  return (int)(wg < 1 ? 1 : wg > CHZ_RAW_MAX_GRID ? CHZ_RAW_MAX_GRID : wg);
+}
+inline int launch_raw_unpack(int format, hipStream_t s, RawUnpackParams p, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
+  const int grid = raw_unpack_grid(p.nf);
+  p.aligned = ((p.wpos & 3) == 0 ? 1 : 0) | (((p.wpos - p.ring_len) & 3) == 0 ? 2 : 0);
+#define X(F) case F: CHZ_LAUNCH(raw_unpack<F>, grid, 256, 0, s, e0, e1, p); return 0;
+  switch (format) { X(RAW_PACKED12) X(RAW_U16) X(RAW_S16) X(RAW_U8) X(RAW_S8) X(RAW_S16_IQ) X(RAW_U8_IQ) X(RAW_S8_IQ) default: break; }
+#undef X
+  return -1;
+}
 // host side of the coherent modes and the PL-tone squelch: what init_pll() (src/osc.c:130-136, called once when the demodulator
 // starts, src/linear.c:41) and the tone set-up of demod_fm() (src/fm.c:50-61) leave behind
 inline DemodExt demod_ext_init() {

@@ -76,6 +76,9 @@ CTCSS_TONES = (67.0, 69.3, 71.9, 74.4, 77.0, 79.7, 82.5, 85.4, 88.5, 91.5, 94.8,
                131.8, 136.5, 141.3, 146.2, 150.0, 151.4, 156.7, 159.8, 162.2, 165.5, 167.9, 171.3, 173.8, 177.3, 179.9, 183.5, 186.2, 189.9, 192.8,
                196.6, 199.5, 203.5, 206.5, 210.7, 213.8, 218.1, 221.3, 225.7, 229.1, 233.6, 237.1, 241.8, 245.5, 250.3, 254.1)
 AFSK_FRAME_MAX = 16384
+# chz_input_write_raw: CHZ_RAW_*, and the bytes a sample takes as (bytes, samples)
+RAW_PACKED12, RAW_U16, RAW_S16, RAW_U8, RAW_S8, RAW_S16_IQ, RAW_U8_IQ, RAW_S8_IQ = range(8)
+RAW_BYTES = {RAW_PACKED12: (12, 8), RAW_U16: (2, 1), RAW_S16: (2, 1), RAW_U8: (1, 1), RAW_S8: (1, 1), RAW_S16_IQ: (4, 1), RAW_U8_IQ: (2, 1), RAW_S8_IQ: (2, 1)}
 PCM_S16BE, PCM_S16LE, PCM_F32LE, PCM_F32BE, PCM_MULAW, PCM_ALAW, PCM_F16LE, PCM_F16BE = 0, 1, 2, 3, 4, 5, 6, 7
 FLAG_NO_SAMPLES, FLAG_MUTE, FLAG_PLL_LOCK, FLAG_TONE_MUTE, FLAG_PENDING = 1, 2, 4, 8, 16
 FRAME_PENDING = 2        # DemodStatus.frame of a filter2 bank's pending block
@@ -93,6 +96,7 @@ SYMBOLS = [
     "chz_bank_read_pcm_open_async", "chz_bank_pcm_open_wait", "chz_bank_pcm_open_times", "chz_step", "chz_run_blocks", "chz_gather_descriptor",
     "chz_bank_set_tuning", "chz_bank_read_power", "chz_bank_read_power_async",
     "chz_input_write_i16", "chz_input_write_i16_device", "chz_input_stats",
+    "chz_input_raw_check", "chz_input_write_raw", "chz_input_write_raw_device", "chz_input_raw_stats",
     "chz_bank_enable_noise", "chz_bank_read_noise", "chz_bank_read_noise_async", "chz_bank_create_real", "chz_bank_set_isb", "chz_bank_set_beam",
     "chz_set_notches_alpha", "chz_slot_sync", "chz_engine_check", "chz_input_seek", "chz_input_mark", "chz_input_mark_wait", "chz_engine_notch_order",
     "chz_bank_set_demod", "chz_bank_pcm_stride", "chz_bank_set_pcm_stride", "chz_bank_read_pcm", "chz_bank_read_pcm_async",
@@ -158,6 +162,10 @@ def lib():
         L.chz_input_write_i16.argtypes = [_vp, _vp, _l, C.c_float, _i]
         L.chz_input_write_i16_device.argtypes = [_vp, _vp, _l, C.c_float, _i]
         L.chz_input_stats.argtypes = [_vp, _i, C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint)]
+        L.chz_input_raw_check.argtypes = [_i, _i, _i, _l]
+        L.chz_input_write_raw.argtypes = [_vp, _i, _i, _vp, _l, _d, C.POINTER(_u)]
+        L.chz_input_write_raw_device.argtypes = [_vp, _i, _i, _vp, _l, _d, C.POINTER(_u)]
+        L.chz_input_raw_stats.argtypes = [_vp, _u, C.POINTER(C.c_ulonglong), C.POINTER(_u), C.POINTER(_u)]
         L.chz_forward.argtypes = [_vp, _u]
         L.chz_set_notches.argtypes = [_vp, _vp, _i, _d]
         L.chz_set_notches_alpha.argtypes = [_vp, _vp, _vp, _i]
@@ -337,6 +345,32 @@ class Engine:
         en, cl = C.c_ulonglong(0), C.c_uint(0)
         _check(lib().chz_input_stats(self._h, slot, C.byref(en), C.byref(cl)))
         return en.value, cl.value
+
+    def write_raw(self, samples, fmt, scale, bits=12, n=None):
+        """Raw A/D samples of one of the RAW_* formats (airspy-unpack.c, hydrasdr.c's and rtlsdr.c's conversion loops), converted on the
+        device into the float ring.  `samples`: an array of the format's own integers (uint32 words for RAW_PACKED12, I and Q interleaved
+        for the I/Q formats) or its bytes; n: the sample count, where it is not all of them.  Returns the write's ticket (raw_stats)."""
+        s = np.ascontiguousarray(samples).reshape(-1).view(np.uint8)
+        num, den = RAW_BYTES.get(fmt, (1, 1))
+        if n is None:
+            n = s.size * den // num
+        elif n > 0 and (n * num + den - 1) // den > s.size:
+            raise ValueError("%d samples of format %d need more than the %d bytes given" % (n, fmt, s.size))
+        t = _u(0)
+        _check(lib().chz_input_write_raw(self._h, fmt, bits, s.ctypes.data, n, float(scale), C.byref(t)))
+        self.sync()       # the caller's buffer may be pageable / reused
+        return t.value
+
+    def write_raw_device(self, dev_ptr, n, fmt, scale, bits=12):
+        t = _u(0)
+        _check(lib().chz_input_write_raw_device(self._h, fmt, bits, dev_ptr, n, float(scale), C.byref(t)))
+        return t.value
+
+    def raw_stats(self, ticket):
+        """(sum of x^2, clipped samples, clipped components) of raw write `ticket`; the last 8 writes' can be read."""
+        en, cs, cc = C.c_ulonglong(0), _u(0), _u(0)
+        _check(lib().chz_input_raw_stats(self._h, ticket, C.byref(en), C.byref(cs), C.byref(cc)))
+        return en.value, cs.value, cc.value
 
     def write_device(self, dev_ptr, n):
         _check(lib().chz_input_write_device(self._h, dev_ptr, n))
