@@ -368,7 +368,27 @@ typedef struct chz_demod_status {
   int tone_mute;        /* FM: 1 while the tone squelch keeps the channel muted */
 } chz_demod_status;
 /* parameters of channels [ch0, ch0+n) from block `job` on (it must not have been enqueued yet); blocktime = radiod's Blocktime.
- * Waits for the demodulator stream only, never for the transform lanes. */
+ * Waits for the demodulator stream only, never for the transform lanes.  A call that is refused has changed nothing.
+ * On a bank that has demodulated blocks already, per channel:
+ *  - the same kind on a channel that is on: decode_radio_commands() writing into the running channel.  Every member is read afresh
+ *    from block `job` on; the demodulator's state goes on.  The AGC owns the gain (`gain` is ignored), the shift oscillator keeps its
+ *    phase when the frequency changes (set_osc, src/osc.c:28-47), a linear PLL that comes on after blocks that ran without it starts
+ *    from lock = 0, lock_count = -limit, rotations = 0 (src/linear.c:150-154) with the loop's state kept, and with the PLL off the status
+ *    keeps pll_snr / pll_cphase / foffset of its last block.  tone_freq is read by the reference once, when demod_fm() starts
+ *    (src/fm.c:50-53), and radiod has no command that changes it live: here a new tone_freq restarts the tone detector as a start leaves
+ *    it (cleared, muted until the new tone has been seen, tone_deviation 0) and everything else goes on.
+ *  - the other kind on a channel that is on: demod_thread() (src/radio.c:907-978) starting the other demodulator on the same chan_t.
+ *    The function locals start over (src/linear.c:41-47, src/fm.c:36-62: init_pll(), am_dc, squelch sequencer and hysteresis,
+ *    phase_memory, de-emphasis state, tone detector muted).  The chan_t members survive: sig.n0, output.gain (after demod_fm(): its
+ *    fixed gain), linear.hangcount, pll.lock / .lock_count / .rotations / .snr / .cphase / .was_on, sig.foffset (one member for the
+ *    linear PLL and demod_fm()), fm.pdeviation, and the shift oscillator, whose phase stands still while demod_fm() runs.  What a
+ *    linear demodulator without its PLL writes every block (lock = 0, lock_count = -limit, rotations = 0) is what the next PLL life
+ *    finds, with or without an FM stretch in between.
+ *  - channels = 0 ends the channel: its status in every slot becomes frame 1 / mute 1 (flags NO_SAMPLES | MUTE), the open read
+ *    does not count it, its PCM rows are left alone.  The reference has no such thing as a re-used channel index; here whoever
+ *    switches the index on again -- in the same call sequence or blocks later -- gets a NEW channel and inherits nothing: n0 restarts at
+ *    the first estimate, the gain at `gain`, PLL and tone records as init_pll() / a start leave them, the shift oscillator at phase 0.
+ *    Channels beyond the old active count (chz_bank_set_active + this call) are new channels in the same sense. */
 int chz_bank_set_demod(chz_engine *e, int bank, unsigned job, int ch0, int n, const chz_demod_params *p, double blocktime);
 /* Demodulating blocks the caller supplies (radiod puts a channel's private second filter, filter2 -- chz_mini_* -- between the
  * channelizer and the demodulator, src/radio.c:1572-1594): chz_bank_write_block stores n channels' olen complex samples

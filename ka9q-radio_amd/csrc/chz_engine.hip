@@ -118,7 +118,9 @@ struct Bank {
   unsigned char* dm_flags = nullptr;     // [ND][cap] one status byte per channel and block
   unsigned char* dm_pcm = nullptr;       // [ND][cap][pcm_stride]
   std::vector<DemodChan> dm_chan_h;      // [cap]
-  struct OscHost { bool init = false; double freq = 0.0, phase0 = 0.0; unsigned job0 = 0; };
+  // (pll_cleared: the channel has been a linear demodulator without PLL since its DemodExt was last brought up to date: chan->pll.lock /
+  //  .lock_count / .rotations are what src/linear.c:150-154 leaves, and the kernels that run without a PLL do not touch DemodExt)
+  struct OscHost { bool init = false; double freq = 0.0, phase0 = 0.0; unsigned job0 = 0; bool pll_cleared = false; };
   std::vector<OscHost> dm_osc;           // [cap] chan->shift with set_osc's phase continuity
   int shared_rows = 0;                   // > 0: the bank's channels share this many response rows (chz_bank_create_shared)
   int dm_on = 0;                         // channels with a demodulator
@@ -1880,7 +1882,11 @@ int chz_bank_set_demod(chz_engine* e, int bank, unsigned job, int ch0, int n, co
   HIPOK(hipStreamSynchronize(e->tail));      // the demodulator stream only: blocks already handed to it keep their parameters
   if (need_ext && !b.dm_ext) {
     // every channel gets the record init_pll() / the tone set-up would leave, whether or not it uses it yet
+    // -- except chan->sig.foffset, which demod_fm() may have left in DemodState: with DemodExt there, that is where a linear channel keeps it
     std::vector<DemodExt> fresh((size_t)b.cap, demod_ext_init());
+    std::vector<DemodState> cur((size_t)b.cap);
+    HIPOK(hipMemcpy(cur.data(), b.dm_state, sizeof(DemodState) * (size_t)b.cap, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < (size_t)b.cap; k++) if (b.dm_chan_h[k].on) fresh[k].foffset = cur[k].foffset;
     HIPOK(hipMalloc((void**)&b.dm_ext, sizeof(DemodExt) * (size_t)b.cap));
     HIPOK(hipMemcpy(b.dm_ext, fresh.data(), sizeof(DemodExt) * (size_t)b.cap, hipMemcpyHostToDevice));
     drop_graph(e);
@@ -1897,12 +1903,22 @@ int chz_bank_set_demod(chz_engine* e, int bank, unsigned job, int ch0, int n, co
     HIPOK(hipDeviceSynchronize());
     drop_graph(e);
   }
-  std::vector<DemodState> init; std::vector<int> init_ch;
+  std::vector<DemodState> init; std::vector<int> init_ch, off_ch;
   for (int i = 0; i < n; i++) {
     const chz_demod_params& q = p[i];
     DemodChan& c = b.dm_chan_h[(size_t)(ch0 + i)];
     const bool was_on = c.on != 0;
-    if (q.channels == 0) { if (was_on) b.dm_on--; c.on = 0; continue; }
+    if (q.channels == 0) {
+      // switched off: the channel's life ends here.  Whoever switches this index on again gets a new channel -- DemodState, DemodExt and
+      // the shift oscillator as a chan_t nobody has run leaves them -- and until then no slot reports the old one open
+      if (was_on) { b.dm_on--; off_ch.push_back(ch0 + i); }
+      c.on = 0; b.dm_osc[(size_t)(ch0 + i)] = Bank::OscHost();
+      continue;
+    }
+    // the other demodulator on a channel that is on: demod_thread() (src/radio.c:907-978) calls demod_fm() / demod_linear() on the
+    // chan_t the other one leaves behind.  The function locals start over, the chan_t members go on
+    const bool restart = was_on && c.kind != q.kind;
+    const double fm_gain_was = restart ? (2 * c.headroom * (double)(int)c.samprate) / c.bandwidth : 0.0;     // chan->output.gain as demod_fm() leaves it (src/fm.c:62,324)
     c.channels = q.channels; c.env = q.env != 0; c.agc = q.agc != 0; c.encoding = q.encoding; c.snr_squelch = q.snr_squelch != 0;
     c.squelch_tail = q.squelch_tail; c.tuned = q.tuned != 0; c.on = 1;
     c.samprate = q.samprate; c.headroom = q.headroom; c.threshold = q.threshold; c.recovery_rate = q.recovery_rate; c.hangtime = q.hangtime;
@@ -1913,7 +1929,8 @@ int chz_bank_set_demod(chz_engine* e, int bank, unsigned job, int ch0, int n, co
       if (!std::isfinite(c.squelch_close) || c.squelch_close == 0) c.squelch_close = 4;
     }
     c.kind = q.kind; c.deemph_rate = q.deemph_rate; c.deemph_gain = q.deemph_gain; c.threshold_extend = q.threshold_extend;
-    const bool pll_was = was_on && c.pll_enable != 0;
+    Bank::OscHost& o = b.dm_osc[(size_t)(ch0 + i)];
+    if (!was_on) o.pll_cleared = false;
     const double tone_was = was_on ? c.tone_freq : 0.0;
     c.pll_enable = q.pll_enable != 0; c.pll_square = q.pll_square != 0; c.pll_loop_bw = q.pll_loop_bw;
     demod_tone_consts(q.kind == CHZ_DEMOD_FM ? q.tone_freq : 0.0, q.samprate, c);
@@ -1922,19 +1939,43 @@ int chz_bank_set_demod(chz_engine* e, int bank, unsigned job, int ch0, int n, co
       if (!was_on) {                                    // a new demodulator: init_pll(), tone squelch muted
         x = demod_ext_init();
         HIPOK(hipMemcpy(b.dm_ext + ch0 + i, &x, sizeof x, hipMemcpyHostToDevice));
-      } else if ((c.pll_enable && !pll_was && c.kind == CHZ_DEMOD_LINEAR) || c.tone_freq != tone_was) {
+      } else if (restart || o.pll_cleared || c.tone_freq != tone_was) {
         HIPOK(hipMemcpy(&x, b.dm_ext + ch0 + i, sizeof x, hipMemcpyDeviceToHost));
-        if (c.pll_enable && !pll_was && c.kind == CHZ_DEMOD_LINEAR) {
-          // what the blocks that ran with the PLL off left behind (src/linear.c:150-154); the loop itself keeps its state
-          x.pll.lock = 0; x.pll.lock_count = -(int)std::lrint(0.5 * (int)q.samprate); x.pll_rotations = 0;
+        if (restart && c.kind == CHZ_DEMOD_LINEAR) {
+          // init_pll() (src/linear.c:41): the loop starts over; chan->pll.lock / .lock_count / .rotations are chan_t's and stay
+          const int lock = x.pll.lock, lock_count = x.pll.lock_count;
+          pll_init(x.pll); x.pll.lock = lock; x.pll.lock_count = lock_count;
         }
-        if (c.tone_freq != tone_was) { x.g_s0 = x.g_s1 = 0.0; x.pl_sample_count = 0; x.old_pl_phase = 0.0; x.tone_mute = 1; x.tone_deviation = 0.0; }
+        if (o.pll_cleared) {
+          // what the blocks that ran as a linear demodulator with the PLL off left behind (src/linear.c:150-154), whatever the channel
+          // becomes now -- a PLL that comes on, or demod_fm(), which never touches them; the loop itself keeps its state
+          x.pll.lock = 0; x.pll.lock_count = -(int)std::lrint(0.5 * (int)q.samprate); x.pll_rotations = 0;
+          o.pll_cleared = false;
+        }
+        // a new tone frequency, or demod_fm() starting (src/fm.c:46-61): the detector cleared, muted until the tone has been seen
+        if (restart || c.tone_freq != tone_was) { x.g_s0 = x.g_s1 = 0.0; x.pl_sample_count = 0; x.old_pl_phase = 0.0; x.tone_mute = 1; x.tone_deviation = 0.0; }
         HIPOK(hipMemcpy(b.dm_ext + ch0 + i, &x, sizeof x, hipMemcpyHostToDevice));
       }
     }
-    // chan->shift: set_osc() keeps the phase when the frequency changes (src/osc.c:28-47); an oscillator at 0 Hz is not stepped (src/linear.c:170)
-    Bank::OscHost& o = b.dm_osc[(size_t)(ch0 + i)];
-    const double f = q.shift / q.samprate;
+    if (c.kind == CHZ_DEMOD_LINEAR && !c.pll_enable) o.pll_cleared = true;
+    if (restart) {
+      // src/linear.c:42-47 / src/fm.c:36,56-58: am_dc, the squelch sequencer and its hysteresis memory, phase_memory and the de-emphasis
+      // state are locals; n0, hangcount, foffset, pdeviation and pll.was_on are chan_t's
+      DemodState st;
+      HIPOK(hipMemcpy(&st, b.dm_state + ch0 + i, sizeof st, hipMemcpyDeviceToHost));
+      st.am_dc = 0.0; st.squelch_open = 1; st.pm_re = 0.0; st.pm_im = 0.0; st.deemph_state = 0.0;
+      st.squelch_state = c.kind == CHZ_DEMOD_FM ? 0 : ((!c.pll_enable && !c.snr_squelch) ? c.squelch_tail + 4 : 0);
+      if (c.kind == CHZ_DEMOD_LINEAR) st.gain = fm_gain_was;
+      if (b.dm_ext) {                                   // chan->sig.foffset is ONE member: the linear PLL's (DemodExt) and demod_fm()'s (DemodState)
+        double* xf = reinterpret_cast<double*>(reinterpret_cast<char*>(b.dm_ext + ch0 + i) + offsetof(DemodExt, foffset));
+        if (c.kind == CHZ_DEMOD_FM) HIPOK(hipMemcpy(&st.foffset, xf, sizeof(double), hipMemcpyDeviceToHost));
+        else HIPOK(hipMemcpy(xf, &st.foffset, sizeof(double), hipMemcpyHostToDevice));
+      }
+      init.push_back(st); init_ch.push_back(ch0 + i);
+    }
+    // chan->shift: set_osc() keeps the phase when the frequency changes (src/osc.c:28-47); an oscillator at 0 Hz is not stepped (src/linear.c:170),
+    // and demod_fm() never steps it: the phase stands still until demod_linear() runs again
+    const double f = q.kind == CHZ_DEMOD_FM ? 0.0 : q.shift / q.samprate;
     if (!o.init) { o.init = true; o.freq = 0.0; o.phase0 = 0.0; o.job0 = job; }
     if (f != o.freq) {
       const double g = (double)(job - o.job0) * (double)dlen;
@@ -1951,6 +1992,22 @@ int chz_bank_set_demod(chz_engine* e, int bank, unsigned job, int ch0, int n, co
       st.squelch_open = 1;                                                              // src/linear.c:47
       init.push_back(st); init_ch.push_back(ch0 + i);
     }
+  }
+  // channels switched off: no slot reports them open any more.  One copy of status records and one of flag bytes per slot and run of
+  // neighbouring channels
+  for (size_t k = 0; k < off_ch.size();) {
+    size_t m = k + 1;
+    while (m < off_ch.size() && off_ch[m] == off_ch[m - 1] + 1) m++;
+    DemodStatus off; memset(&off, 0, sizeof off); off.frame = 1; off.mute = 1;
+    const std::vector<DemodStatus> sts(m - k, off);
+    const std::vector<unsigned char> fls(m - k, (unsigned char)(CHZ_FLAG_NO_SAMPLES | CHZ_FLAG_MUTE));
+    for (int s = 0; s < CHZ_ND; s++) {
+      const size_t so = (size_t)s * b.cap + (size_t)off_ch[k];
+      if (b.pcm_copying[s]) HIPOK(hipEventSynchronize(b.ev_pcm[s]));      // a read of the slot on the copy stream sees the block it asked for
+      HIPOK(hipMemcpy(b.dm_status + so, sts.data(), sizeof(DemodStatus) * (m - k), hipMemcpyHostToDevice));
+      HIPOK(hipMemcpy(b.dm_flags + so, fls.data(), m - k, hipMemcpyHostToDevice));
+    }
+    k = m;
   }
   b.dm_pll_lin = 0; b.dm_fm_pll = 0; b.dm_fm_tone = 0; b.dm_lin = 0; b.dm_fm = 0; b.dm_fm_nopll = 0;
   for (const DemodChan& dc : b.dm_chan_h) {

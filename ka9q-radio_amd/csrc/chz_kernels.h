@@ -2500,7 +2500,11 @@ __global__ void __launch_bounds__(64, CHZ_LIN_WAVES) demod_lin_lanes(DemodParams
     if (pll) {
       const DemodExt* __restrict__ ext = p.ext + ch;
       pll_snr = ext->pll_snr; pll_cph = ext->pll_cphase; pll_foff = ext->foffset; pll_lock = ext->pll.lock; pll_rot = ext->pll_rotations;
-    }
+    } else if (p.ext != nullptr) {
+      // the PLL is off: chan->pll.snr / .cphase and chan->sig.foffset keep what its last block left (lock and rotations are cleared, src/linear.c:150-154)
+      const DemodExt* __restrict__ ext = p.ext + ch;
+      pll_snr = ext->pll_snr; pll_cph = ext->pll_cphase; pll_foff = ext->foffset;
+    } else pll_foff = st.foffset;                            // (no PLL state in the bank: what demod_fm() left, if it ever ran)
   }
   // chan->shift (src/linear.c:168-172): the phasor at a tile's first sample from the closed form, stepped in double inside the tile
   const bool rot = active && osc_freq != 0.0;
@@ -3124,7 +3128,11 @@ __global__ void __launch_bounds__(64) demod_linear_tail(DemodParams p) {
     }
     CHZ_WAVE_SYNC();
     pll_snr = __shfl(pll_snr, 0);                          // the squelch decisions below are taken by every lane
-  }
+  } else if (p.ext != nullptr) {
+    // the PLL is off: chan->pll.snr / .cphase and chan->sig.foffset keep what its last block left (lock and rotations are cleared, src/linear.c:150-154)
+    const DemodExt* __restrict__ ext = p.ext + ch;
+    pll_snr = ext->pll_snr; pll_cph = ext->pll_cphase; pll_foff = ext->foffset;
+  } else pll_foff = st.foffset;                              // (no PLL state in the bank: what demod_fm() left, if it ever ran)
   // chan->shift (src/linear.c:168-172): this lane's phasor at its first sample from the closed form, then stepped in double
   const bool rot = c.osc_freq != 0.0;
   double c0 = 1.0, s0 = 0.0, c1 = 1.0, s1 = 0.0;

@@ -753,8 +753,25 @@ static double pll_run(o_pll *q, double phase) {                                 
   return q->u;
 }
 
+/* The chan_t members that outlive a demodulator: demod_thread() (src/radio.c:907-978) calls demod_linear() / demod_fm() again on the
+   SAME chan_t when one returns (a change of demodulator type or sample rate, src/radio_status.c:614-632), and between the two calls it
+   only frees the output queue, the Opus encoder and the filter output and re-inits the fine-tuning oscillator (filter.remainder = NAN).
+   So everything the demodulators keep in chan_t survives, whichever of the two wrote it last:
+     chan->sig.n0 (the smoothing goes on), chan->output.gain, chan->linear.hangcount, chan->shift (phase and frequency),
+     chan->pll.pll, chan->pll.lock / .lock_count / .rotations / .snr / .cphase / .was_on, chan->sig.foffset, chan->fm.pdeviation
+   and every function local starts over (src/linear.c:41-47, src/fm.c:36-62). */
+typedef struct o_chan {
+  double n0, gain;
+  int hangcount;
+  chzo_downconv shift;
+  o_pll pll;
+  int pll_lock, pll_lock_count, pll_rotations, pll_was_on;
+  double pll_snr, pll_cphase, foffset, pdeviation;
+} o_chan;
+
 struct chzo_lindemod {
   chzo_lindemod_params p;
+  o_chan carry;            /* what the demodulator started from: the members demod_linear() never touches (was_on, pdeviation) pass through */
   /* demod_linear's locals and the chan_t fields it updates */
   double gain;             /* chan->output.gain */
   int hangcount;           /* chan->linear.hangcount */
@@ -768,18 +785,34 @@ struct chzo_lindemod {
   double pll_snr, pll_cphase, foffset;           /* chan->pll.snr, .cphase, chan->sig.foffset */
 };
 
-chzo_lindemod *chzo_lindemod_create(const chzo_lindemod_params *p) {
+/* demod_linear() entered on a chan_t in state *c (src/linear.c:27-47): the locals fresh, init_pll(), everything else as found */
+static chzo_lindemod *lindemod_start(const chzo_lindemod_params *p, const o_chan *c) {
   chzo_lindemod *d = (chzo_lindemod *)calloc(1, sizeof *d);
   if (!d) return NULL;
   d->p = *p;
-  d->gain = p->gain;
-  d->n0 = NAN;
+  d->carry = *c;
+  d->gain = c->gain; d->n0 = c->n0; d->hangcount = c->hangcount; d->shift = c->shift;
+  d->pll_lock = c->pll_lock; d->pll_lock_count = c->pll_lock_count; d->pll_rotations = c->pll_rotations;
+  d->pll_snr = c->pll_snr; d->pll_cphase = c->pll_cphase; d->foffset = c->foffset;
   d->squelch_state = (!p->pll_enable && !p->snr_squelch) ? p->squelch_tail + 4 : 0;   /* src/linear.c:46 */
   pll_init(&d->pll);                                                        /* :41 */
-  d->squelch_open = 1;                                                      /* :47 */
+  d->squelch_open = 1;                                                      /* :47; am_dc = 0 (:42) */
   return d;
 }
+static void lindemod_leave(const chzo_lindemod *d, o_chan *c) {
+  *c = d->carry;
+  c->gain = d->gain; c->n0 = d->n0; c->hangcount = d->hangcount; c->shift = d->shift; c->pll = d->pll;
+  c->pll_lock = d->pll_lock; c->pll_lock_count = d->pll_lock_count; c->pll_rotations = d->pll_rotations;
+  c->pll_snr = d->pll_snr; c->pll_cphase = d->pll_cphase; c->foffset = d->foffset;
+}
+static void chan_new(o_chan *c, double gain) { memset(c, 0, sizeof *c); c->n0 = NAN; c->gain = gain; }   /* a chan_t nobody has run yet */
+chzo_lindemod *chzo_lindemod_create(const chzo_lindemod_params *p) {
+  o_chan c; chan_new(&c, p->gain);
+  return lindemod_start(p, &c);
+}
 void chzo_lindemod_delete(chzo_lindemod *d) { free(d); }
+/* decode_radio_commands() wrote into the running channel: the loop reads every one of these members afresh each block.  The gain
+   is the AGC's (p->gain is what the demodulator STARTED with); samprate is the loop's local copy (src/linear.c:27). */
 void chzo_lindemod_set_params(chzo_lindemod *d, const chzo_lindemod_params *p) { double g = d->gain; d->p = *p; d->p.gain = g; }
 
 static int pcm_bytes_per_sample(int enc) {
@@ -1065,6 +1098,7 @@ double chzo_fm_snr(double r) {
 
 struct chzo_fmdemod {
   chzo_lindemod_params p;
+  o_chan carry;               /* what the demodulator started from; .gain follows chan->output.gain (:62, :325) */
   double n0;                  /* chan->sig.n0 */
   double pm_re, pm_im;        /* phase_memory (src/fm.c:36) */
   double deemph_state;        /* :57 */
@@ -1077,20 +1111,61 @@ struct chzo_fmdemod {
   int pl_sample_count, tone_mute;
   double old_pl_phase, tone_deviation;
 };
-chzo_fmdemod *chzo_fmdemod_create(const chzo_lindemod_params *p) {
-  chzo_fmdemod *d = (chzo_fmdemod *)calloc(1, sizeof *d);
-  if (!d) return NULL;
-  d->p = *p; d->n0 = NAN;
-  if (!isfinite(d->p.squelch_open) || d->p.squelch_open == 0) d->p.squelch_open = 6.3;      /* :38-41 */
-  if (!isfinite(d->p.squelch_close) || d->p.squelch_close == 0) d->p.squelch_close = 4;
+static void fm_tone_setup(chzo_fmdemod *d) {                               /* :46-61: detector state as a start leaves it */
+  d->g_s0 = d->g_s1 = 0; d->pl_sample_count = 0; d->old_pl_phase = 0;
   d->tone_mute = 1;                                                          /* :61 muted until the tone is detected */
-  if (p->tone_freq != 0) {                                                   /* :50-53 init_goertzel(tone_freq / samprate) */
-    const double f = p->tone_freq / (int)p->samprate;
+  d->g_coeff = d->g_cfr = d->g_cfi = 0;
+  if (d->p.tone_freq != 0) {                                                 /* :50-53 init_goertzel(tone_freq / samprate) */
+    const double f = d->p.tone_freq / (int)d->p.samprate;
     d->g_coeff = 2 * cos(2 * M_PI * f); d->g_cfr = cos(2 * M_PI * f); d->g_cfi = -sin(2 * M_PI * f);
   }
+}
+/* demod_fm() entered on a chan_t in state *c (src/fm.c:25-62) */
+static chzo_fmdemod *fmdemod_start(const chzo_lindemod_params *p, const o_chan *c) {
+  chzo_fmdemod *d = (chzo_fmdemod *)calloc(1, sizeof *d);
+  if (!d) return NULL;
+  d->p = *p;
+  d->carry = *c;
+  d->n0 = c->n0; d->foffset = c->foffset; d->pdeviation = c->pdeviation; d->pll = c->pll; d->pll_was_on = c->pll_was_on;
+  if (!isfinite(d->p.squelch_open) || d->p.squelch_open == 0) d->p.squelch_open = 6.3;      /* :38-41 */
+  if (!isfinite(d->p.squelch_close) || d->p.squelch_close == 0) d->p.squelch_close = 4;
+  fm_tone_setup(d);
+  d->carry.gain = (2 * p->headroom * (int)p->samprate) / p->bandwidth;       /* :62 chan->output.gain, whatever the squelch does later */
   return d;
 }
+static void fmdemod_leave(const chzo_fmdemod *d, o_chan *c) {
+  *c = d->carry;
+  c->n0 = d->n0; c->foffset = d->foffset; c->pdeviation = d->pdeviation; c->pll = d->pll; c->pll_was_on = d->pll_was_on;
+}
+chzo_fmdemod *chzo_fmdemod_create(const chzo_lindemod_params *p) {
+  o_chan c; chan_new(&c, 0.0);
+  return fmdemod_start(p, &c);
+}
 void chzo_fmdemod_delete(chzo_fmdemod *d) { free(d); }
+/* decode_radio_commands() wrote into the running channel.  demod_fm()'s loop reads afresh each block: squelch.open / .close / .tail and
+   .snr_enable (:111,:149-152), filter.min_IF / max_IF (:106,:324), output.headroom (:324), fm.rate / .gain (:311-314), fm.threshold
+   (:189,:215), pll.enable (:176, with the was_on handling of :178-184,:209 in the block function) and, in send_output(), the encoding.
+   The thresholds are taken as given: the defaults of :38-41 are applied when the demodulator starts and not again.
+   chan->fm.tone_freq is read ONCE, at :50-53, and radiod has no command that changes it while the demodulator runs; a change of it
+   here is therefore defined by the engine (chz_bank_set_demod, include/chz_engine.h): the tone detector starts over as a restart
+   would leave it (:46-61: cleared, integration counter and phase memory 0, muted until the new tone has been seen,
+   chan->fm.tone_deviation 0), and everything else -- squelch sequencer, phase memory, de-emphasis, statistics -- goes on. */
+void chzo_fmdemod_set_params(chzo_fmdemod *d, const chzo_lindemod_params *p) {
+  const double tone_was = d->p.tone_freq;
+  d->p = *p;
+  if (p->tone_freq != tone_was) { fm_tone_setup(d); d->tone_deviation = 0; }
+}
+/* the demodulator returns and demod_thread() starts the next one on the same chan_t: exactly one of from_lin / from_fm is given */
+chzo_lindemod *chzo_lindemod_restart(const chzo_lindemod_params *p, const chzo_lindemod *from_lin, const chzo_fmdemod *from_fm) {
+  o_chan c;
+  if (from_lin) lindemod_leave(from_lin, &c); else if (from_fm) fmdemod_leave(from_fm, &c); else chan_new(&c, p->gain);
+  return lindemod_start(p, &c);
+}
+chzo_fmdemod *chzo_fmdemod_restart(const chzo_lindemod_params *p, const chzo_lindemod *from_lin, const chzo_fmdemod *from_fm) {
+  o_chan c;
+  if (from_lin) lindemod_leave(from_lin, &c); else if (from_fm) fmdemod_leave(from_fm, &c); else chan_new(&c, 0.0);
+  return fmdemod_start(p, &c);
+}
 
 int chzo_fmdemod_block(chzo_fmdemod *d, const float *buf, int N, double bb_power, double n0_est, double blocktime,
                        unsigned char *pcm, chzo_lindemod_status *st) {
@@ -1229,6 +1304,7 @@ int chzo_fmdemod_block(chzo_fmdemod *d, const float *buf, int N, double bb_power
     }
   }
   const double gain = (2 * c->headroom * samprate) / c->bandwidth;           /* :325 */
+  d->carry.gain = gain;
   double output_energy = 0;
   for (int n = 0; n < N; n++) {
     const double s = gain * baseband[n];

@@ -146,6 +146,14 @@ chzo_fmdemod *chzo_fmdemod_create(const chzo_lindemod_params *p);
 void chzo_fmdemod_delete(chzo_fmdemod *d);
 int chzo_fmdemod_block(chzo_fmdemod *d, const float *buf, int N, double bb_power, double n0_est, double blocktime,
                        unsigned char *pcm, chzo_lindemod_status *st);
+/* the chan_t members demod_fm()'s loop reads every block; a change of tone_freq (which the reference reads once, src/fm.c:50-53)
+   restarts the tone detector muted and nothing else */
+void chzo_fmdemod_set_params(chzo_fmdemod *d, const chzo_lindemod_params *p);
+/* demod_thread() (src/radio.c:907-978) starting the next demodulator on the chan_t the previous one leaves behind: fresh function
+   locals (src/linear.c:41-47, src/fm.c:36-62), the chan_t members carried over from from_lin or from_fm (give one; neither = a new
+   chan_t, as *_create) */
+chzo_lindemod *chzo_lindemod_restart(const chzo_lindemod_params *p, const chzo_lindemod *from_lin, const chzo_fmdemod *from_fm);
+chzo_fmdemod *chzo_fmdemod_restart(const chzo_lindemod_params *p, const chzo_lindemod *from_lin, const chzo_fmdemod *from_fm);
 
 #ifdef __cplusplus
 }

@@ -533,19 +533,38 @@ def pcm_bytes(encoding, nsamples):
     return (1 if encoding in (PCM_MULAW, PCM_ALAW) else 2 if encoding in (PCM_S16BE, PCM_S16LE, PCM_F16LE, PCM_F16BE) else 4) * nsamples
 
 
+def _restart_from(previous):
+    return (previous._h, None) if isinstance(previous, LinDemod) else (None, previous._h)
+
+
+def demod(params, previous=None):
+    """The restated demodulator of params.kind."""
+    return (FmDemod if params.kind == DEMOD_FM else LinDemod)(params, previous)
+
+
+def _switch_args(switches):
+    switches = sorted(switches or [], key=lambda s: s[0])
+    blocks = np.array([b for b, _ in switches], np.int32)
+    arr = (LinParams * max(1, len(switches)))(*[q for _, q in switches])
+    return len(switches), blocks, arr
+
+
 class LinDemod:
     """Restated per-block work of demod_linear() (oracle/chz_oracle.c:chzo_lindemod_block)."""
 
-    def __init__(self, params):
+    def __init__(self, params, previous=None):
+        """previous: the LinDemod / FmDemod that ran on this chan_t until now (demod_thread() starting the next demodulator)."""
         L = oracle()
         L.chzo_lindemod_create.restype = _vp; L.chzo_lindemod_create.argtypes = [C.POINTER(LinParams)]
         L.chzo_lindemod_delete.argtypes = [_vp]
         L.chzo_lindemod_set_params.argtypes = [_vp, C.POINTER(LinParams)]
         L.chzo_lindemod_block.argtypes = [_vp, _vp, _i, _d, _d, _d, _vp, C.POINTER(LinStatus)]
+        L.chzo_lindemod_restart.restype = _vp; L.chzo_lindemod_restart.argtypes = [C.POINTER(LinParams), _vp, _vp]
         self.p = params
-        self._h = L.chzo_lindemod_create(C.byref(params))
+        self._h = L.chzo_lindemod_restart(C.byref(params), *_restart_from(previous)) if previous is not None else L.chzo_lindemod_create(C.byref(params))
 
     def set_params(self, params):
+        """decode_radio_commands() wrote into the running channel (everything but the running gain)."""
         self.p = params
         oracle().chzo_lindemod_set_params(self._h, C.byref(params))
 
@@ -568,13 +587,20 @@ class LinDemod:
 class FmDemod:
     """Restated per-block work of demod_fm() (oracle/chz_oracle.c:chzo_fmdemod_block)."""
 
-    def __init__(self, params):
+    def __init__(self, params, previous=None):
         L = oracle()
         L.chzo_fmdemod_create.restype = _vp; L.chzo_fmdemod_create.argtypes = [C.POINTER(LinParams)]
         L.chzo_fmdemod_delete.argtypes = [_vp]
         L.chzo_fmdemod_block.argtypes = [_vp, _vp, _i, _d, _d, _d, _vp, C.POINTER(LinStatus)]
+        L.chzo_fmdemod_set_params.argtypes = [_vp, C.POINTER(LinParams)]
+        L.chzo_fmdemod_restart.restype = _vp; L.chzo_fmdemod_restart.argtypes = [C.POINTER(LinParams), _vp, _vp]
         self.p = params
-        self._h = L.chzo_fmdemod_create(C.byref(params))
+        self._h = L.chzo_fmdemod_restart(C.byref(params), *_restart_from(previous)) if previous is not None else L.chzo_fmdemod_create(C.byref(params))
+
+    def set_params(self, params):
+        """The members demod_fm()'s loop reads every block; a new tone_freq restarts the tone detector muted."""
+        self.p = params
+        oracle().chzo_fmdemod_set_params(self._h, C.byref(params))
 
     def block(self, samples, bb_power, n0_est, blocktime=0.02):
         buf = np.ascontiguousarray(samples, np.complex64)
@@ -598,21 +624,23 @@ def have_ref_fm():
 _ref_fm = None
 
 
-def ref_fm_run(params, baseband, bb_power, n0_smoothed, blocktime=0.02):
-    """The reference's OWN demod_fm() (oracle/ref_fm_wrap.c).  Returns dict of per-block arrays."""
+def ref_fm_run(params, baseband, bb_power, n0_smoothed, blocktime=0.02, switches=None):
+    """The reference's OWN demod_fm() (oracle/ref_fm_wrap.c).  Returns dict of per-block arrays.  switches: [(block, LinParams)] written
+    into the running channel in front of those blocks (the members the loop reads every block); rows are then 4 * N bytes."""
     global _ref_fm
     if _ref_fm is None:
         _ref_fm = C.CDLL(os.path.join(ORACLE_DIR, "_ref", "libka9q_ref_fm.so"))
-        _ref_fm.reffm_run.argtypes = [C.POINTER(LinParams), _d, _i, _i, _vp, _vp, _vp, _vp, _i] + [_vp] * 8
+        _ref_fm.reffm_run_switched.argtypes = [C.POINTER(LinParams), _d, _i, _i, _vp, _vp, _vp, _vp, _i] + [_vp] * 8 + [_i, _vp, _vp]
     bb = np.ascontiguousarray(baseband, np.complex64)
     nb, n = bb.shape
-    stride = pcm_bytes(params.encoding, n)
+    stride = 4 * n if switches else pcm_bytes(params.encoding, n)
+    nsw, sw_blocks, sw_params = _switch_args(switches)
     out = dict(pcm=np.zeros((nb, stride), np.uint8), frame=np.zeros(nb, np.int32), mute=np.zeros(nb, np.int32), power=np.zeros(nb),
                gain=np.zeros(nb), snr=np.zeros(nb), foffset=np.zeros(nb), pdev=np.zeros(nb), tonedev=np.zeros(nb))
     bp = np.ascontiguousarray(bb_power, np.float64); n0 = np.ascontiguousarray(n0_smoothed, np.float64)
-    r = _ref_fm.reffm_run(C.byref(params), float(blocktime), nb, n, _fptr(bb), _fptr(bp), _fptr(n0), _fptr(out["pcm"]), stride,
-                          _fptr(out["frame"]), _fptr(out["mute"]), _fptr(out["power"]), _fptr(out["gain"]), _fptr(out["snr"]),
-                          _fptr(out["foffset"]), _fptr(out["pdev"]), _fptr(out["tonedev"]))
+    r = _ref_fm.reffm_run_switched(C.byref(params), float(blocktime), nb, n, _fptr(bb), _fptr(bp), _fptr(n0), _fptr(out["pcm"]), stride,
+                                   _fptr(out["frame"]), _fptr(out["mute"]), _fptr(out["power"]), _fptr(out["gain"]), _fptr(out["snr"]),
+                                   _fptr(out["foffset"]), _fptr(out["pdev"]), _fptr(out["tonedev"]), nsw, _fptr(sw_blocks), C.cast(sw_params, _vp))
     assert r == 0
     return out
 
@@ -624,23 +652,26 @@ def have_ref_linear():
 _ref_linear = None
 
 
-def ref_linear_run(params, baseband, bb_power, n0_smoothed, blocktime=0.02, pll_out=None):
+def ref_linear_run(params, baseband, bb_power, n0_smoothed, blocktime=0.02, pll_out=None, switches=None):
     """The reference's OWN demod_linear() (oracle/ref_linear_wrap.c) over nblocks blocks of baseband[nblocks][N];
     n0_smoothed = chan->sig.n0 as downconvert() leaves it.  Returns (pcm[nblocks][bytes], frame, mute, out_power, gain);
-    pll_out (float64[nblocks][5], optional) receives chan->pll.snr, .lock, .cphase, .rotations and chan->sig.foffset per block."""
+    pll_out (float64[nblocks][5], optional) receives chan->pll.snr, .lock, .cphase, .rotations and chan->sig.foffset per block.
+    switches: [(block, LinParams)] written into the running channel in front of those blocks; rows are then 8 * N bytes."""
     global _ref_linear
     if _ref_linear is None:
         _ref_linear = C.CDLL(os.path.join(ORACLE_DIR, "_ref", "libka9q_ref_linear.so"))
-        _ref_linear.reflin_run.argtypes = [C.POINTER(LinParams), _d, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]
+        _ref_linear.reflin_run_switched.argtypes = [C.POINTER(LinParams), _d, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]
     bb = np.ascontiguousarray(baseband, np.complex64)
     nb, n = bb.shape
-    stride = pcm_bytes(params.encoding, n * params.channels)
+    stride = 8 * n if switches else pcm_bytes(params.encoding, n * params.channels)
+    nsw, sw_blocks, sw_params = _switch_args(switches)
     pcm = np.zeros((nb, stride), np.uint8)
     frame = np.zeros(nb, np.int32); mute = np.zeros(nb, np.int32)
     power = np.zeros(nb); gain = np.zeros(nb)
     bp = np.ascontiguousarray(bb_power, np.float64); n0 = np.ascontiguousarray(n0_smoothed, np.float64)
-    r = _ref_linear.reflin_run(C.byref(params), float(blocktime), nb, n, _fptr(bb), _fptr(bp), _fptr(n0), _fptr(pcm), stride,
-                               _fptr(frame), _fptr(mute), _fptr(power), _fptr(gain), _fptr(pll_out) if pll_out is not None else None)
+    r = _ref_linear.reflin_run_switched(C.byref(params), float(blocktime), nb, n, _fptr(bb), _fptr(bp), _fptr(n0), _fptr(pcm), stride,
+                                        _fptr(frame), _fptr(mute), _fptr(power), _fptr(gain), _fptr(pll_out) if pll_out is not None else None,
+                                        nsw, _fptr(sw_blocks), C.cast(sw_params, _vp))
     assert r == 0
     return pcm, frame, mute, power, gain
 

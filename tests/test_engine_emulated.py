@@ -4,7 +4,8 @@
 stream, inline-master pools, every C-ABI entry point -- is compiled UNMODIFIED with g++ against tests/hipemu (the kernels run on the
 fiber emulator, the HIP runtime calls on a synchronous stand-in, tests/hipemu/hip/hip_host_stub.h) into a test-only library behind
 the same C ABI.  The parity tests that normally need an MI355X (tests/test_gpu_parity.py, test_gpu_pipeline.py, test_golden.py) are
-then run against it in a child process (tests/test_gpu_demod_shapes.py and tests/test_gpu_pcm_edges.py with them -- the latter is where
+then run against it in a child process (tests/test_gpu_demod_shapes.py, tests/test_gpu_demod_midstream.py -- chz_bank_set_demod on a running
+bank -- and tests/test_gpu_pcm_edges.py with them -- the latter is where
 the kernels' host body of demod_f16_bits, which only this build compiles, meets every binary16 rounding tie): what they check on the device -- outputs against the oracle, through the C ABI -- they check
 here for the engine's orchestration, without a GPU.  Not a fallback: the library carries a marker symbol and engine.py refuses to load
 it unless CHZ_ALLOW_EMULATED_ENGINE=1 (set here and nowhere else)."""
@@ -51,13 +52,13 @@ def test_engine_orchestration_on_the_emulator(emulated_engine):
     env = dict(os.environ, CHZ_LIB=emulated_engine, CHZ_ALLOW_EMULATED_ENGINE="1")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), os.path.join(ROOT, "tests", "test_gpu_pipeline.py"),
                         os.path.join(ROOT, "tests", "test_golden.py"), os.path.join(ROOT, "tests", "test_gpu_demod_shapes.py"),
-                        os.path.join(ROOT, "tests", "test_gpu_pcm_edges.py"), "-m", "gpu", "-q", "-x", "--timeout", "300", "-p", "no:cacheprovider", "-k", "not (%s)" % SKIP,
+                        os.path.join(ROOT, "tests", "test_gpu_pcm_edges.py"), os.path.join(ROOT, "tests", "test_gpu_demod_midstream.py"), "-m", "gpu", "-q", "-x", "--timeout", "300", "-p", "no:cacheprovider", "-k", "not (%s)" % SKIP,
                         "-n", str(max(1, min(6, (os.cpu_count() or 2) - 1)))],      # the tests are independent processes' worth of work: pytest-xdist
                        capture_output=True, text=True, env=env, timeout=1500, cwd=ROOT)
     tail = r.stdout.strip().splitlines()[-1] if r.stdout.strip() else ""
     assert r.returncode == 0, (tail, r.stdout[-3000:], r.stderr[-1500:])
     m = re.search(r"(\d+) passed", tail)
-    assert m and int(m.group(1)) >= 75, tail               # 60 and the 15 of tests/test_gpu_pcm_edges.py
+    assert m and int(m.group(1)) >= 96, tail               # 60, the 15 of tests/test_gpu_pcm_edges.py and the 21 of tests/test_gpu_demod_midstream.py
 
 
 def test_dropin_on_the_emulated_engine(emulated_engine, tmp_path):

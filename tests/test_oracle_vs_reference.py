@@ -698,6 +698,111 @@ def _fm_pll_and_tone_against_reference(kw, tone_sent, N, bt):
 
 
 # ------------------------------------------------------------------------------------------------
+# parameters written into a RUNNING demodulator (decode_radio_commands() -> chan_t, read afresh by the loops each block): the
+# reference's own demod_linear() / demod_fm(), whose downconvert() stub writes the scenario's parameter sets in front of the given blocks,
+# against the restatement's set_params -- which is what makes set_params a reference for chz_bank_set_demod on a running bank
+# (tests/test_gpu_demod_midstream.py, same scenarios: tests/demod_midstream_cases.py).  Comparison rules and tolerances: those of
+# test_linear_demodulator_matches_reference_linear_c / test_linear_pll_matches_reference_linear_c / test_fm_demodulator_matches_reference_fm_c /
+# test_fm_pll_and_tone_squelch_match_reference_fm_c above.
+# ------------------------------------------------------------------------------------------------
+import demod_midstream_cases as mc
+
+
+def _smoothed(n0_est):
+    n0s = np.zeros(len(n0_est)); s = np.nan
+    for b in range(len(n0_est)):                                     # src/radio.c:1466-1473, Power_alpha = 0.10
+        s = n0_est[b] if np.isnan(s) else s + 0.10 * (n0_est[b] - s)
+        n0s[b] = s
+    return n0s
+
+
+def _cmp_frame(p, pcm, want, tol_f):
+    if p.encoding in (ol.PCM_MULAW, ol.PCM_ALAW):
+        assert np.mean(pcm != want) < 0.01                           # a code flips only where a sample sits on a step
+    elif p.encoding in (ol.PCM_S16BE, ol.PCM_S16LE):
+        dt = ">i2" if p.encoding == ol.PCM_S16BE else "<i2"
+        a, w = pcm.view(dt).astype(np.int32), want.view(dt).astype(np.int32)
+        assert np.abs(a - w).max() <= 1 and np.mean(a != w) == 0
+    else:
+        dt = ">f4" if p.encoding == ol.PCM_F32BE else "<f4"
+        a, w = pcm.view(dt).astype(np.float64), want.view(dt).astype(np.float64)
+        assert np.abs(a - w).max() <= tol_f * max(np.abs(w).max(), 1e-30)
+
+
+def _no_f16(sets):
+    """The reference's gcc build packs no binary16 (test_f16_packing_equals_the_references_import_h pins that packer): the reference
+    loop and the restatement both take F32LE where the scenario says F16LE -- the switch itself, at the same block, stays."""
+    out = []
+    for b, q in sets:
+        if q.encoding in (ol.PCM_F16LE, ol.PCM_F16BE):
+            q = ol.LinParams.from_buffer_copy(bytes(q)); q.encoding = ol.PCM_F32LE
+        out.append((b, q))
+    return out
+
+
+@pytest.mark.skipif(not ol.have_ref_linear(), reason="oracle/_ref/libka9q_ref_linear.so not built (needs the reference's sources)")
+@pytest.mark.parametrize("N", [240, 250])
+@pytest.mark.parametrize("name", [sc["name"] for sc in mc.LINEAR])
+def test_linear_set_params_matches_the_running_reference_loop(oracle_built, name, N):
+    c = mc.scenario(name, N)
+    sets = _no_f16(c["sets"])
+    bb, power, est = c["bb"], c["power"], c["est"]
+    pll_r = np.zeros((mc.NBLK, 5))
+    pcm_r, frame_r, mute_r, pow_r, gain_r = ol.ref_linear_run(sets[0][1], bb, power, _smoothed(est), mc.BT, pll_out=pll_r, switches=sets[1:])
+    d = ol.LinDemod(sets[0][1])
+    S = []
+    for b in range(mc.NBLK):
+        p = mc.params_at(sets, b)
+        if p is not d.p:
+            d.set_params(p)
+        pcm, st = d.block(bb[b], power[b], est[b], mc.BT)
+        S.append(mc.Rec(pcm, st))
+        pll = any(q.pll_enable for _, q in sets)                     # (the loop's state goes on mattering after it was switched off)
+        assert st.frame == frame_r[b] and st.mute == mute_r[b], (b, st.frame, frame_r[b], st.mute, mute_r[b])
+        assert st.gain == pytest.approx(gain_r[b], rel=1e-7 if pll else 1e-12), b
+        assert st.output_power == pytest.approx(pow_r[b], rel=1e-6 if pll else 2e-7 if any(q.env for _, q in sets) else 1e-12, abs=1e-300), b
+        assert st.pll_lock == int(pll_r[b, 1]) and st.pll_rotations == int(pll_r[b, 3]), b
+        if pll:                                                      # with the PLL off: chan->pll.snr / .cphase / sig.foffset as its last block left them
+            assert st.pll_snr == pytest.approx(pll_r[b, 0], rel=1e-6, abs=1e-9)
+            dphi = (st.pll_cphase - pll_r[b, 2] + np.pi) % (2 * np.pi) - np.pi
+            assert abs(dphi) < 1e-6
+            assert st.foffset == pytest.approx(pll_r[b, 4], rel=1e-6, abs=1e-6)
+        if st.frame == ol.FRAME_DATA:
+            _cmp_frame(p, pcm, pcm_r[b][:pcm.size], 2e-6 if pll else 2e-7)
+    if not any(q.encoding != r.encoding for (_, q), (_, r) in zip(sets, c["sets"])):
+        assert c["sc"]["cover"](S, c["T"])                             # the run compared is the run that reaches the scenario's branch
+
+
+# (the scenarios that change tone_freq are not here: the reference reads it once, src/fm.c:50-53 -- see chzo_fmdemod_set_params)
+@pytest.mark.skipif(not ol.have_ref_fm(), reason="oracle/_ref/libka9q_ref_fm.so not built (needs the reference's sources)")
+@pytest.mark.parametrize("N", [240, 250])
+@pytest.mark.parametrize("name", [sc["name"] for sc in mc.FM if not any("tone_freq" in upd for _, upd in sc["sw"])])
+def test_fm_set_params_matches_the_running_reference_loop(oracle_built, name, N):
+    c = mc.scenario(name, N)
+    sets = c["sets"]
+    bb, power, est = c["bb"], c["power"], c["est"]
+    ref = ol.ref_fm_run(sets[0][1], bb, power, _smoothed(est), mc.BT, switches=sets[1:])
+    d = ol.FmDemod(sets[0][1])
+    S = []
+    for b in range(mc.NBLK):
+        p = mc.params_at(sets, b)
+        if p is not d.p:
+            d.set_params(p)
+        pcm, st = d.block(bb[b], power[b], est[b], mc.BT)
+        S.append(mc.Rec(pcm, st))
+        assert st.frame == ref["frame"][b] and st.mute == ref["mute"][b], (b, st.frame, st.mute, ref["frame"][b], ref["mute"][b])
+        assert st.snr == pytest.approx(ref["snr"][b], rel=1e-6, abs=1e-12)
+        assert st.tone_deviation == pytest.approx(ref["tonedev"][b], rel=1e-5, abs=1e-6)
+        if st.frame == ol.FRAME_DATA:
+            assert st.output_power == pytest.approx(ref["power"][b], rel=2e-6)
+            assert st.gain == pytest.approx(ref["gain"][b], rel=1e-14)
+            assert st.foffset == pytest.approx(ref["foffset"][b], rel=1e-5, abs=1e-5)
+            assert st.pdeviation == pytest.approx(ref["pdev"][b], rel=1e-5, abs=1e-3)
+            _cmp_frame(p, pcm, ref["pcm"][b][:pcm.size], 4e-6)
+    assert c["sc"]["cover"](S, c["T"])
+
+
+# ------------------------------------------------------------------------------------------------
 # randomised sweeps: the restated demodulators against the reference's own code over parameter combinations nobody picked by hand
 # ------------------------------------------------------------------------------------------------
 def _cmp_pcm(p, got, want, tol_f):
