@@ -667,6 +667,57 @@ int chz_ctcss_set_response(chz_ctcss *m, int inst, const float *resp);          
 int chz_ctcss_execute(chz_ctcss *m, int n, const int *inst, const void *const *samples, int samples_on_device, chz_ctcss_status *status,
                       double *const *energies);
 
+/* ---- Pooled FM-multiplex decoders: stereod's and rdsd's decode() loops (src/stereod.c:373-408 and :460-513, src/rdsd.c:385-413 and
+ * :465-500) from a session's 16-bit FM multiplex at 384 kHz -- a discriminator's output -- to its 16-bit output at 48 kHz ------
+ * A pool is one geometry: (block time, kind, input byte order).  The block time alone fixes the rest as both programs do:
+ * L = lrint(384000 blocktime), M = L + 1, N = 2 L, slaves of olen = L / 8 samples (P = 2 olen), rotated by quantum * lrint(f / (hzperbin
+ * * quantum)) bins with quantum = 2 and the integer hzperbin = 384000 / N.  One launch serves every session that is due, one workgroup
+ * per request: the L samples are converted and appended to the session's L old ones, the REAL master and its slaves (chz_rmini_*'s
+ * transform and gather rules, the responses from the host) decimate, and the per-sample loop runs behind them.
+ *   CHZ_MPX_STEREO: samples as (float)((1. / 32767) * s); a REAL mono slave at shift 0, COMPLEX pilot and L-R slaves at 19 and 38 kHz; per
+ *   output sample, in double, the pilot squared and normalised (where its magnitude is > 0, else L-R counts as 0 and the sample is
+ *   counted in zero_pilot), 2 Im(conj(subc) stereo), left = mono + that and right = mono - that, each side through
+ *   state = state * rate + gain * (1 - rate) * x and, as a float, through scaleclip() (src/misc.h:252-254); big-endian, L R interleaved.
+ *   CHZ_MPX_RDS: samples as ldexp(s, -15); COMPLEX slaves for the pilot and at 57 kHz; the output is scaleclip() of the 57 kHz slave's
+ *   re and im, big-endian -- all rdsd does today; nothing reads the pilot slave, so the device does not compute it.
+ * The decoder is a recurrence over blocks: the filter's history, the two de-emphasis states and the parameters live on the device, per
+ * instance; chz_mpx_add leaves history and states zero and the parameters stereod's own.
+ * What stays with the caller: RTP (both ways) and collecting a stream's packets into rows of L samples.
+ * Limits, refused at chz_mpx_create / chz_mpx_check and nowhere else: what chz_rmini_create refuses for that master and its slaves
+ * (25 ms gives N = 19200 > 16384); 384000 % N != 0 (3 ms: the reference would truncate hzperbin silently); a shift that does not land
+ * on its frequency (2.5 ms: 19 kHz falls between even bins of 200 Hz); a kind or byte order that is neither value; a block time that is
+ * not finite and positive.  1, 2, 5 (both programs' own), 10 and 20 ms pass.
+ * Option mpx_deemph_lanes (chz_set_option, read by chz_mpx_create): how many lanes share a block's de-emphasis recurrences, 64 (default)
+ * down to 1 (one lane walks the block in the reference's order). */
+#define CHZ_MPX_STEREO 0
+#define CHZ_MPX_RDS    1
+#define CHZ_MPX_BE 0   /* samples as RTP carries them */
+#define CHZ_MPX_LE 1
+typedef struct chz_mpx chz_mpx;
+typedef struct chz_mpx_params { double deemph_rate, deemph_gain; } chz_mpx_params;   /* after chz_mpx_add: stereod's own, exp(-1 / (75e-6 * 48000)) and 4; rate 0 = no memory.  RDS ignores them */
+typedef struct chz_mpx_status {
+  int zero_pilot;                    /* STEREO: samples of this block whose squared pilot had magnitude 0 (the reference's a > 0 test failed); RDS: 0 */
+  int pad;
+  double deemph_left, deemph_right;  /* the states as the block leaves them; RDS: 0 */
+} chz_mpx_status;
+int  chz_mpx_check(double blocktime, int kind, int byte_order);            /* would chz_mpx_create take this? 0, or < 0 and chz_last_error(); touches no device */
+int  chz_mpx_create(chz_mpx **out, double blocktime, int kind, int byte_order, int capacity, int device);
+void chz_mpx_destroy(chz_mpx *m);
+int  chz_mpx_capacity(const chz_mpx *m);
+int  chz_mpx_geometry(const chz_mpx *m, int out7[7]);                      /* L, M, N, olen, P, pilot_shift, subc_shift */
+int  chz_mpx_add(chz_mpx *m);                                              /* -> instance index; all state zero, as a fresh decode() thread */
+int  chz_mpx_release(chz_mpx *m, int inst);
+int  chz_mpx_set_params(chz_mpx *m, int inst, const chz_mpx_params *p);    /* 0 <= rate < 1, both finite; in effect from the next block, the states carry over */
+int  chz_mpx_set_response(chz_mpx *m, int inst, int slave, const float *resp);   /* STEREO: 0 mono, 1 pilot, 2 L-R; RDS: 0 pilot, 1 rds; P complex, as chz_rmini_set_response */
+/* One block of n decoders, one H2D, ONE launch and one D2H of status records and PCM per chunk of `capacity`: instance inst[i] (at most
+ * once in a call) takes the L 16-bit samples at samples[i] in the pool's byte order -- host memory (samples_on_device = 0), or device
+ * memory that is complete before the call (1; read in place, 2-byte aligned).  pcm[i] receives 4 olen bytes.  audio may be NULL;
+ * audio[i], where not NULL, receives the 2 olen floats the packer was fed -- (float)left, (float)right interleaved, or the 57 kHz
+ * slave's re / im pairs -- (a second D2H, made only for a chunk in which a request asks).  Every request is checked before the first
+ * launch: a refused call has written nothing and advanced no state.  Synchronous, thread-safe. */
+int  chz_mpx_execute(chz_mpx *m, int n, const int *inst, const void *const *samples, int samples_on_device,
+                     void *const *pcm, float *const *audio, chz_mpx_status *status);
+
 /* ---- Welch power spectra of the raw input: radiod's wideband spectrum analyser (wideband_poll(), src/spectrum.c:308-522) on the
  * samples the engine's input ring holds (float REAL, float COMPLEX or the int16 of chz_input_write_i16).  A bank holds `capacity`
  * analysers sharing one fft_n (= lrint(samprate / rbw): any length from 8 to 2^20 points; one with a prime factor above 13 runs as

@@ -452,6 +452,7 @@ struct ChzOptions {
   int allow_fault_injection = 0;  // ... only with this set as well
   int welch_packed = 1;       // chz_welch_create: real front end, even fft_n -- 1: half-length packed transform + Hermitian split (measured faster at every size), 0: full-length complex transform
   int wfm_deemph_lanes = 64;  // chz_wfm_create: lanes of wavefront 0 that share a block's de-emphasis recurrence (1: one lane walks it as the reference does; DESIGN.md section 8 has both times)
+  int mpx_deemph_lanes = 64;  // chz_mpx_create: the same choice for stereod's two de-emphasis recurrences (DESIGN.md section 7 has both times)
   char launch_id[64] = {0};   // chz_comm_create_file: the id of this launch (ranks of another launch's rendezvous file are refused)
 };
 static ChzOptions g_opt;
@@ -476,6 +477,7 @@ extern "C" int chz_set_option(const char* name, const char* value) {
   else if (n == "allow_fault_injection") g_opt.allow_fault_injection = d ? 0 : (value[0] == '1');
   else if (n == "welch_packed") g_opt.welch_packed = d ? def.welch_packed : (iv != 0);
   else if (n == "wfm_deemph_lanes") g_opt.wfm_deemph_lanes = (d || iv < 1 || iv > 64) ? def.wfm_deemph_lanes : iv;
+  else if (n == "mpx_deemph_lanes") g_opt.mpx_deemph_lanes = (d || iv < 1 || iv > 64) ? def.mpx_deemph_lanes : iv;
   else if (n == "launch_id") snprintf(g_opt.launch_id, sizeof g_opt.launch_id, "%s", d ? "" : value);
   else return fail(-1, "unknown option '%s'", name);
   return 0;
@@ -2552,4 +2554,5 @@ int chz_run_blocks(chz_engine* e, unsigned job0, int nblocks, int mode, int inst
 #include "chz_wfm.inc"
 #include "chz_afsk.inc"
 #include "chz_ctcss.inc"
+#include "chz_mpx.inc"
 #include "chz_welch.inc"

@@ -4210,6 +4210,180 @@ __global__ void __launch_bounds__(1024) ctcss_ovs(CtcssParams p) {
 }
 
 // ------------------------------------------------------------------------------
+// stereod's and rdsd's decode() loops (src/stereod.c:460-513, src/rdsd.c:465-500): the FM multiplex -- a discriminator's output as 16-bit
+// PCM at 384 kHz -- to 48 kHz stereo PCM (STEREO) or to the 57 kHz RDS subcarrier's baseband (RDS).  One workgroup per request.  The front
+// is afsk_ovs's: the block's L samples are converted (STEREO: (float)((1. / 32767) * s), :461-462; RDS: ldexp(s, -15), :466), put behind
+// the session's M - 1 = L old ones (HBM) and run through rmini_ovs's forward transform and split; then the slaves, one after the other
+// (mini_fft, rmini_split, rmini_slave: called, not changed).
+//   STEREO: mono (REAL, shift 0), the pilot and L-R (COMPLEX, spun down from 19 and 38 kHz) leave their olen samples in LDS behind the
+//   transform's buffers, as wfm_ovs lays them out.  Lane n is output sample n of the stereo matrix, in double: the pilot squared and
+//   normalised by its cabs() where that is > 0 (:490-500; a sample where it is not counts in zero_pilot and carries no L-R), 2 Im(conj(subc)
+//   stereo), left and right.  The two de-emphasis recurrences state = state * rate + gain (1 - rate) x (:504-505,510-511; stereod's form,
+//   not wfm's) are first-order and linear: `deemph_lanes` lanes of wavefront 0 each reduce a run of consecutive samples to an affine
+//   map, lane 0 composes the maps, the lanes replay their runs from the right start with the reference's own statement (deemph_lanes = 1:
+//   one lane walks the block as the reference does).
+//   RDS: nothing reads the pilot slave (:493-496 are comments), so only the 57 kHz slave runs; its re / im pairs are packed as they are.
+// The packer is scaleclip() (src/misc.h:252-254): x >= 1 -> 32767, x <= -1 -> -32767, else the FLOAT product 32767 x truncated toward
+// zero; big-endian, two samples a lane in one 32-bit store.  The floats the packer was fed also leave where the launch asks (p.audio).
+// LDS (float2 units): forward A = [0, H), B = [H, 2H), H = L; then S = [0, H], Y / W = two P-point buffers, the slaves' samples from
+// out_off, CHZ_MPX_RED doubles of scratch at red_off.  The tail reuses S for the 2 olen doubles the recurrences walk (2 olen <= H).
+// ------------------------------------------------------------------------------
+#define CHZ_MPX_RED 256
+#define CHZ_MPX_STEREO_K 0
+#define CHZ_MPX_RDS_K 1
+struct MpxState { double deemph_left, deemph_right, rate, gain; };      // the recurrences' states and chz_mpx_params
+struct MpxReq { const unsigned short* samples; int inst, pad; };        // L 16-bit samples (device), any 2-byte alignment
+struct MpxStatusK { int zero_pilot, pad; double deemph_left, deemph_right; };
+struct MpxParams {
+  const MpxReq* req;      // [nreq]
+  MpxState* state;        // [ninst]
+  float* hist;            // [ninst][L]
+  unsigned char* pcm;     // [nreq][4 olen]
+  float* audio;           // [nreq][2 olen], or null: nobody asked for the floats
+  MpxStatusK* status;     // [nreq]
+  const float2* tw_split; // [N/2 + 1] e^{-2 pi i k / N}
+  MiniParams fwd;         // the N/2-point forward transform
+  RminiSlave s[3];        // STEREO: mono (REAL), pilot, L-R; RDS: pilot, rds; m.resp = the slave's row of instance 0 in [ninst][nslaves][P]
+  ChanDesc d[3];          // their gathers (row: nslaves x the instance, filled in per request)
+  int N, olen, out_off, red_off, deemph_lanes, kind, big_endian, nslaves;
+};
+
+__device__ __forceinline__ unsigned mpx_scaleclip(float x) {                // the 16 bits of scaleclip(x)
+  const float prod = 32767.0f * x;                                         // INT16_MAX * x: a float product
+  const int v = (x >= 1.0f) ? 32767 : (x <= -1.0f) ? -32767 : (int)prod;
+  return (unsigned)v & 0xffffu;
+}
+// state = state * rate + g1 * x over v[0, n) with stride 2 doubles, in place; `y0` is the state before the block, the state after it is
+// returned in every thread.  Wavefront 0 works, everybody meets at the barriers (wfm_deemph's scheme with stereod's statement).
+__device__ __forceinline__ double mpx_deemph(double* v, int n, double y0, double rate, double g1, int lanes, double* red, int tid) {
+  const int seg = (n + lanes - 1) / lanes;
+  const int n0 = tid * seg, n1 = n0 + seg < n ? n0 + seg : n;
+  if (lanes > 1) {
+    if (tid < lanes) {                                                     // this run as the affine map y -> a y + b
+      double a = 1.0, b = 0.0;
+      for (int i = n0; i < n1; i++) { double t = b * rate, u = g1 * v[2 * i]; CHZ_ROUNDED_F64(t); CHZ_ROUNDED_F64(u); b = t + u; a *= rate; }
+      red[2 * tid] = a; red[2 * tid + 1] = b;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      double y = y0;
+      for (int l = 0; l < lanes; l++) { const double a = red[2 * l], b = red[2 * l + 1]; red[2 * l] = y; y = a * y + b; }
+    }
+    __syncthreads();
+    if (tid < lanes) y0 = red[2 * tid];
+    __syncthreads();
+  }
+  if (tid < lanes) {
+    double y = y0;
+    for (int i = n0; i < n1; i++) { double t = y * rate, u = g1 * v[2 * i]; CHZ_ROUNDED_F64(t); CHZ_ROUNDED_F64(u); y = t + u; v[2 * i] = y; }
+    if (n1 == n && n0 < n) red[0] = y;                                      // the lane that holds the last sample
+  }
+  __syncthreads();
+  const double last = red[0];
+  __syncthreads();
+  return last;
+}
+
+__global__ void __launch_bounds__(1024) mpx_ovs(MpxParams p) {
+  HIP_DYNAMIC_SHARED(float2, lds)
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int H = p.N / 2, L = H, olen = p.olen;                             // M = L + 1: the window is L old and L new samples
+  const MpxReq rq = p.req[blockIdx.x];
+  const bool rds = p.kind == CHZ_MPX_RDS_K;
+  // ---- the window: the L old samples, then the block's L; the new block replaces the history (thread n alone touches hist[n])
+  float* Af = reinterpret_cast<float*>(lds);
+  float* __restrict__ hist = p.hist + (size_t)rq.inst * L;
+  for (int n = tid; n < L; n += nthr) {
+    unsigned v = rq.samples[n];
+    if (p.big_endian) v = ((v & 0xffu) << 8) | (v >> 8);
+    const short s = (short)v;
+    const float c = rds ? (float)s * (1.0f / 32768.0f) : (float)((1.0 / 32767) * (double)s);
+    Af[n] = hist[n];
+    Af[L + n] = c;
+    hist[n] = c;
+  }
+  __syncthreads();
+  // ---- the filter: rmini_ovs's forward transform and split, then the slaves
+  float2* A = lds;
+  float2* B = lds + H;
+  const float2* Z = mini_fft<-1>(A, B, p.fwd, tid, nthr);
+  float2* S = lds;
+  rmini_split(Z, S, p.tw_split, H, tid, nthr);
+  float2* Y = lds + H + 1;
+  const int no_isb = 0;
+  const int drop = p.s[0].m.N - olen;                                      // (the slaves are of one size)
+  unsigned* __restrict__ o = reinterpret_cast<unsigned*>(p.pcm + (size_t)blockIdx.x * 4 * olen);
+  float2* __restrict__ au = p.audio ? reinterpret_cast<float2*>(p.audio) + (size_t)blockIdx.x * olen : nullptr;
+  MpxStatusK* __restrict__ so = p.status + blockIdx.x;
+  if (rds) {                                                               // ---- src/rdsd.c:489,498-499
+    ChanDesc d = p.d[1]; d.row = p.nslaves * rq.inst;
+    const float2* T = rmini_slave(S, Y, p.s[1], d, no_isb, H + 1, tid, nthr) + drop;
+    for (int n = tid; n < olen; n += nthr) {
+      const float2 v = T[n];
+      const unsigned a = mpx_scaleclip(v.x), b = mpx_scaleclip(v.y);
+      o[n] = ((a >> 8) | ((a & 0xffu) << 8)) | (((b >> 8) | ((b & 0xffu) << 8)) << 16);      // htons() of each, re first
+      if (au) au[n] = v;
+    }
+    if (tid == 0) *so = MpxStatusK{0, 0, 0.0, 0.0};
+    return;
+  }
+  // ---- src/stereod.c:482-484
+  float* monoO = reinterpret_cast<float*>(lds + p.out_off);
+  float2* pilO = lds + p.out_off + (olen + 1) / 2;
+  float2* lmrO = pilO + olen;
+  double* red = reinterpret_cast<double*>(lds + p.red_off);
+  ChanDesc d = p.d[0]; d.row = p.nslaves * rq.inst;
+  const float2* T = rmini_slave(S, Y, p.s[0], d, no_isb, H + 1, tid, nthr);     // L+R, 50 Hz - 15 kHz, shift 0
+  for (int n = tid; n < olen; n += nthr) monoO[n] = T[drop + n].x;
+  __syncthreads();
+  d = p.d[1]; d.row = p.nslaves * rq.inst;
+  T = rmini_slave(S, Y, p.s[1], d, no_isb, H + 1, tid, nthr);              // the pilot spun down from 19 kHz
+  for (int n = tid; n < olen; n += nthr) pilO[n] = T[drop + n];
+  __syncthreads();
+  d = p.d[2]; d.row = p.nslaves * rq.inst;
+  T = rmini_slave(S, Y, p.s[2], d, no_isb, H + 1, tid, nthr);              // L-R spun down from 38 kHz
+  for (int n = tid; n < olen; n += nthr) lmrO[n] = T[drop + n];
+  __syncthreads();
+  // ---- the stereo matrix (:490-502,508), lane n is sample n; S is done with once the last gather has run
+  MpxState* __restrict__ stp = p.state + rq.inst;
+  const MpxState st = *stp;
+  double* sv = reinterpret_cast<double*>(lds);
+  double zeros = 0.0;
+  for (int n = tid; n < olen; n += nthr) {
+    const double pr = pilO[n].x, pi = pilO[n].y;
+    double rr = pr * pr, ii = pi * pi, ri = pr * pi, ir = pi * pr;         // subc_phasor *= subc_phasor, every product rounded
+    CHZ_ROUNDED_F64(rr); CHZ_ROUNDED_F64(ii); CHZ_ROUNDED_F64(ri); CHZ_ROUNDED_F64(ir);
+    const double sr = rr - ii, si = ri + ir;
+    const double a = hypot(sr, si);                                        // cabs()
+    double lmr = 0.0;
+    if (a > 0) {
+      const double cr = sr / a, ci = si / a;
+      double x = cr * (double)lmrO[n].y, y = ci * (double)lmrO[n].x;
+      CHZ_ROUNDED_F64(x); CHZ_ROUNDED_F64(y);
+      lmr = 2.0 * (x - y);                                                 // 2 Im(conj(subc) stereo)
+    } else zeros += 1.0;
+    const double m = monoO[n];
+    sv[2 * n] = m + lmr; sv[2 * n + 1] = m - lmr;
+  }
+  __syncthreads();
+  const double nzero = wfm_reduce<0>(zeros, red, tid, nthr);
+  // ---- de-emphasis (:504-505,510-511): Deemph_gain * (1 - Deemph_rate) is formed first, as the reference's expression associates
+  const double g1 = st.gain * (1 - st.rate);
+  const double yl = mpx_deemph(sv, olen, st.deemph_left, st.rate, g1, p.deemph_lanes, red, tid);
+  const double yr = mpx_deemph(sv + 1, olen, st.deemph_right, st.rate, g1, p.deemph_lanes, red, tid);
+  for (int n = tid; n < olen; n += nthr) {
+    const float2 v = make_float2((float)sv[2 * n], (float)sv[2 * n + 1]);
+    const unsigned a = mpx_scaleclip(v.x), b = mpx_scaleclip(v.y);
+    o[n] = ((a >> 8) | ((a & 0xffu) << 8)) | (((b >> 8) | ((b & 0xffu) << 8)) << 16);        // htons() of each, left first
+    if (au) au[n] = v;
+  }
+  if (tid == 0) {
+    stp->deemph_left = yl; stp->deemph_right = yr;
+    *so = MpxStatusK{(int)nzero, 0, yl, yr};
+  }
+}
+
+// ------------------------------------------------------------------------------
 // K3+K4 for ANY P without a prime factor above 13 -- the sizes the register-tiled chan_ifft / chan_c2r menu does not hold
 // (wfm's 384 kHz channel on a 20 ms block with overlap 5 is P = 9600, src/wfm.c:37-39; odd sample rates).  One workgroup
 // per channel: the gather x response of src/filter.c:728-911 lands in LDS in FFT order (COMPLEX or REAL output, ISB

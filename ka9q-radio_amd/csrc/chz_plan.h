@@ -585,4 +585,62 @@ inline int ctcss_check_geom(double samprate, int ntones, const double* tones, in
   return 0;
 }
 
+// ---- pooled FM-multiplex decoders (mpx_ovs): stereod's and rdsd's geometry from the block time alone (src/stereod.c:373-408, src/rdsd.c:385-413) --
+// out7: L = lrint(384000 blocktime), M = L + 1, N = 2 L, olen = L * 48000 / 384000, P = N olen / L, pilot_shift, subc_shift (38 kHz for
+// STEREO, 57 kHz for RDS), the shifts as quantum * lrint(f / (hzperbin * quantum)) with quantum = N / (M - 1) = 2 and hzperbin = 384000 / N
+// in integer division, as the reference writes it.  Refuses a kind or byte order that is neither value, a block time that is not finite
+// and positive, what rmini_check_geom refuses for that REAL master with its slaves (STEREO: REAL, COMPLEX, COMPLEX; RDS: COMPLEX, COMPLEX),
+// 384000 % N != 0 (the reference would truncate hzperbin silently) and a shift that does not land on its frequency ("Assume the remainder
+// is zero", :403-404).  Leaves 1, 2, 5, 10 and 20 ms blocks among the round ones.
+#define CHZ_MPX_KIND_STEREO 0
+#define CHZ_MPX_KIND_RDS 1
+#define CHZ_MPX_COMPOSITE_RATE 384000            // Composite_samprate / In_samprate
+#define CHZ_MPX_AUDIO_RATE 48000                 // Audio_samprate / Out_samprate
+#define CHZ_MPX_RED_DOUBLES 256                  // reduction and scan scratch behind the buffers (CHZ_MPX_RED, chz_kernels.h)
+inline int mpx_check_geom(double blocktime, int kind, int byte_order, int out7[7], char* why, size_t why_len) {
+  if (kind != CHZ_MPX_KIND_STEREO && kind != CHZ_MPX_KIND_RDS) { snprintf(why, why_len, "kind %d is neither CHZ_MPX_STEREO nor CHZ_MPX_RDS", kind); return -1; }
+  if (byte_order != 0 && byte_order != 1) { snprintf(why, why_len, "byte order %d is neither CHZ_MPX_BE nor CHZ_MPX_LE", byte_order); return -1; }
+  if (!std::isfinite(blocktime) || !(blocktime > 0)) { snprintf(why, why_len, "bad block time %g s: it must be finite and positive", blocktime); return -1; }
+  const double Ld = CHZ_MPX_COMPOSITE_RATE * blocktime;
+  const int L = Ld > 1e6 ? 1000000 : (int)lrint(Ld), M = L + 1;              // (beyond a million samples rmini_check_geom refuses all the same)
+  const int olen = (int)((long long)L * CHZ_MPX_AUDIO_RATE / CHZ_MPX_COMPOSITE_RATE);
+  const bool stereo = kind == CHZ_MPX_KIND_STEREO;
+  const int nsl = stereo ? 3 : 2;
+  const int olens[3] = {olen, olen, olen};
+  const int types[3] = {stereo ? CHZ_IN_REAL : CHZ_IN_COMPLEX, CHZ_IN_COMPLEX, CHZ_IN_COMPLEX};
+  int P[3] = {};
+  const int rc = rmini_check_geom(L, M, nsl, olens, types, P, why, why_len);
+  if (rc) return rc;
+  const int N = L + M - 1;
+  if (CHZ_MPX_COMPOSITE_RATE % N != 0) {
+    snprintf(why, why_len, "a %g s block has N = %d points and 384000 %% %d != 0: the reference's integer hzperbin would be truncated", blocktime, N, N);
+    return -3;
+  }
+  const int hzperbin = CHZ_MPX_COMPOSITE_RATE / N, quantum = N / (M - 1);
+  const int freq[2] = {19000, stereo ? 38000 : 57000};
+  int shift[2];
+  for (int k = 0; k < 2; k++) {
+    shift[k] = quantum * (int)lrint((double)freq[k] / ((double)hzperbin * quantum));
+    if ((long long)shift[k] * hzperbin != freq[k]) {
+      snprintf(why, why_len, "a %g s block puts %d Hz between the even bins of %d Hz: shift %d lands on %lld Hz and no mop-up oscillator is provided", blocktime,
+               freq[k], hzperbin, shift[k], (long long)shift[k] * hzperbin);
+      return -3;
+    }
+  }
+  if (out7) { out7[0] = L; out7[1] = M; out7[2] = N; out7[3] = olen; out7[4] = P[0]; out7[5] = shift[0]; out7[6] = shift[1]; }
+  return 0;
+}
+// LDS layout of mpx_ovs in float2 units, after wfm_launch_geom: the slaves' samples start at out_off (STEREO: mono as floats, pilot and
+// L-R complex; RDS packs straight from the transform's buffer), the double scratch at red_off; threads as rmini_ovs.  5 ms: the forward
+// transform's 2 x 1920 points outweigh the 3481 behind it, 30,720 + 2,048 B = 32 KB -- four workgroups still share a CU.
+inline void mpx_launch_geom(int N, int P, int olen, int kind, int* out_off, int* red_off, size_t* lds, int* threads) {
+  const int H = N / 2;
+  *out_off = H + 1 + 2 * P;
+  const int behind = *out_off + (kind == CHZ_MPX_KIND_STEREO ? (olen + 1) / 2 + 2 * olen : 0);
+  *red_off = 2 * H > behind ? 2 * H : behind;
+  *lds = sizeof(f2) * (size_t)*red_off + sizeof(double) * CHZ_MPX_RED_DOUBLES;
+  const int q = (H / 4 + 63) / 64 * 64, top = *lds <= 40 * 1024 ? 256 : 1024;
+  *threads = q < 64 ? 64 : (q > top ? top : q);
+}
+
 }  // namespace chz

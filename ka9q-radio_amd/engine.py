@@ -68,7 +68,19 @@ class CtcssStatus(C.Structure):
     _fields_ = [("tone_index", _i), ("current_index", _i), ("energy", _d)]
 
 
+class MpxParams(C.Structure):
+    """chz_mpx_params: stereod's Deemph_rate and Deemph_gain (an RDS pool ignores them)."""
+    _fields_ = [("deemph_rate", _d), ("deemph_gain", _d)]
+
+
+class MpxStatus(C.Structure):
+    """chz_mpx_status: one block of one FM-multiplex decoder."""
+    _fields_ = [("zero_pilot", _i), ("pad", _i), ("deemph_left", _d), ("deemph_right", _d)]
+
+
 AFSK_BE, AFSK_LE = 0, 1
+MPX_STEREO, MPX_RDS = 0, 1
+MPX_BE, MPX_LE = 0, 1
 CTCSS_BE, CTCSS_LE = 0, 1
 CTCSS_TABLE_MAX = 64
 # the table a CtcssPool searches when it is given none: ctcss's own (src/ctcss.c:62-69)
@@ -109,6 +121,8 @@ SYMBOLS = [
     "chz_afsk_set_response", "chz_afsk_execute",
     "chz_ctcss_check", "chz_ctcss_create", "chz_ctcss_destroy", "chz_ctcss_capacity", "chz_ctcss_geometry", "chz_ctcss_add", "chz_ctcss_release",
     "chz_ctcss_set_response", "chz_ctcss_execute",
+    "chz_mpx_check", "chz_mpx_create", "chz_mpx_destroy", "chz_mpx_capacity", "chz_mpx_geometry", "chz_mpx_add", "chz_mpx_release", "chz_mpx_set_params",
+    "chz_mpx_set_response", "chz_mpx_execute",
     "chz_comm_barrier", "chz_comm_allreduce_max", "chz_spectrum_broadcast", "chz_spectrum_exchange_rows", "chz_run_blocks_sharded",
     "chz_comm_create_local", "chz_spectrum_broadcast_local", "chz_set_option",
     "chz_welch_create", "chz_welch_destroy", "chz_welch_set_window", "chz_welch_configure", "chz_welch_poll", "chz_welch_read", "chz_welch_read_async",
@@ -219,6 +233,16 @@ def lib():
         L.chz_ctcss_release.argtypes = [_vp, _i]
         L.chz_ctcss_set_response.argtypes = [_vp, _i, _vp]
         L.chz_ctcss_execute.argtypes = [_vp, _i, _vp, _vp, _i, _vp, _vp]
+        L.chz_mpx_check.argtypes = [_d, _i, _i]
+        L.chz_mpx_create.argtypes = [C.POINTER(_vp), _d, _i, _i, _i, _i]
+        L.chz_mpx_destroy.argtypes = [_vp]; L.chz_mpx_destroy.restype = None
+        L.chz_mpx_capacity.argtypes = [_vp]
+        L.chz_mpx_geometry.argtypes = [_vp, C.POINTER(_i * 7)]
+        L.chz_mpx_add.argtypes = [_vp]
+        L.chz_mpx_release.argtypes = [_vp, _i]
+        L.chz_mpx_set_params.argtypes = [_vp, _i, C.POINTER(MpxParams)]
+        L.chz_mpx_set_response.argtypes = [_vp, _i, _i, _vp]
+        L.chz_mpx_execute.argtypes = [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp]
         L.chz_comm_unique_id.argtypes = [_vp]
         L.chz_comm_create.argtypes = [C.POINTER(_vp), _i, _i, _vp, _i]
         L.chz_comm_create_file.argtypes = [C.POINTER(_vp), _i, _i, C.c_char_p, _i, _d]
@@ -1146,6 +1170,81 @@ class CtcssPool:
     def close(self):
         if self._h:
             lib().chz_ctcss_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MpxPool:
+    """Pool of FM-multiplex decoders of one block time, kind and byte order (stereod's and rdsd's decode() loops, src/stereod.c, src/rdsd.c):
+    the 16-bit multiplex at 384 kHz in rows of L samples in, 4 olen bytes of big-endian 16-bit PCM (L R interleaved, or the 57 kHz
+    subcarrier's re im) and a status record per block out.  RTP and collecting packets into rows stay with the caller."""
+
+    def __init__(self, blocktime, capacity, kind=MPX_STEREO, byte_order=MPX_BE, device=0):
+        self._h = _vp()
+        _check(lib().chz_mpx_create(C.byref(self._h), float(blocktime), kind, byte_order, capacity, device))
+        g = (_i * 7)()
+        _check(lib().chz_mpx_geometry(self._h, C.byref(g)))
+        self.geometry = dict(zip(("L", "M", "N", "olen", "P", "pilot_shift", "subc_shift"), (int(v) for v in g)))
+        self.L, self.M, self.N, self.olen, self.P = (self.geometry[k] for k in ("L", "M", "N", "olen", "P"))
+        self.blocktime, self.capacity, self.kind, self.byte_order = float(blocktime), capacity, kind, byte_order
+        self.nslaves = 3 if kind == MPX_STEREO else 2
+        self.last_raw = None
+
+    @staticmethod
+    def check(blocktime, kind=MPX_STEREO, byte_order=MPX_BE):
+        """Would a pool of this geometry be created?  Raises ChzError with the reason if not; touches no device."""
+        _check(lib().chz_mpx_check(float(blocktime), kind, byte_order))
+
+    def add(self):
+        return _check(lib().chz_mpx_add(self._h))
+
+    def release(self, inst):
+        _check(lib().chz_mpx_release(self._h, inst))
+
+    def set_params(self, inst, params):
+        _check(lib().chz_mpx_set_params(self._h, inst, C.byref(params)))
+
+    def set_response(self, inst, slave, resp):
+        r = np.ascontiguousarray(resp, np.complex64).reshape(-1)
+        assert r.shape[0] == self.P
+        _check(lib().chz_mpx_set_response(self._h, inst, slave, r.ctypes.data))
+
+    def execute(self, insts, samples, audio=False, on_device=False, fill=None):
+        """samples: [n][L] 16-bit words in the pool's byte order as they lie in memory (an int16 / uint16 array or a list of n rows, of which
+        one may be None: a null row, which the call refuses), or (on_device) n device addresses of L such words each, complete before the call.
+        audio: also return the 2 olen floats per request that the packer was fed.  fill: what the PCM (and float) buffers hold before the call;
+        the PCM buffers are 16 bytes longer than a row and kept whole in `self.last_raw`, the float buffers in `self.last_raw_audio`.
+        -> (list of n PCM byte arrays of 4 olen bytes, list of n float32 arrays of 2 olen or None, MpxStatus array)."""
+        insts = np.ascontiguousarray(insts, np.int32)
+        n = insts.shape[0]
+        if on_device:
+            sp = (_vp * n)(*[int(a) if a else None for a in samples])
+        else:
+            rows = [None if r is None else np.ascontiguousarray(r).view(np.uint16).reshape(self.L) for r in samples]
+            sp = (_vp * n)(*[None if r is None else r.ctypes.data for r in rows])
+        nb = 4 * self.olen
+        raw = np.empty((n, nb + 16), np.uint8) if fill is None else np.full((n, nb + 16), fill, np.uint8)
+        pp = (_vp * n)(*[raw[i].ctypes.data for i in range(n)])
+        fraw, ap = None, None
+        if audio:
+            fraw = np.empty((n, 2 * self.olen + 4), np.float32)
+            if fill is not None:
+                fraw.view(np.uint8)[:] = fill
+            ap = (_vp * n)(*[fraw[i].ctypes.data for i in range(n)])
+        status = (MpxStatus * n)()
+        self.last_raw, self.last_raw_audio = raw, fraw
+        _check(lib().chz_mpx_execute(self._h, n, insts.ctypes.data, sp, int(bool(on_device)), pp, ap, status))
+        pcm = [raw[i, :nb].copy() for i in range(n)]
+        return pcm, ([fraw[i, :2 * self.olen].copy() for i in range(n)] if audio else None), status
+
+    def close(self):
+        if self._h:
+            lib().chz_mpx_destroy(self._h)
             self._h = _vp()
 
     def __del__(self):
