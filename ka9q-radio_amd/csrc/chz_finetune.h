@@ -28,6 +28,19 @@ struct FineHost {
 
 static inline double frac1(double x) { return x - std::floor(x); }
 
+// The angle, in cycles, of the phasor set_osc gets from cispi(2 x) (src/osc.c:39,44).  The reference's sincospi() first reduces its
+// argument into [0, 2) half-turns (mod2, src/sincospi.c:12-19): a NEGATIVE 2x has 2.0 added and is thereby rounded to a multiple of
+// 2^-52 half-turns -- nothing for a frequency, but a Doppler rate of -1e-10 cycles/sample^2 is moved by up to 1e-6 of itself, which
+// the oscillator then integrates twice (a float ulp of phase after some 30000 samples).  What follows the reduction is exact in the
+// angle, so this is the step the reference's oscillator really takes.
+static inline double osc_step_cycles(double x) {
+  double y = 2.0 * x;
+  y -= std::floor(y * 0.5) * 2.0;
+  if (y < 0) y += 2.0;
+  if (y >= 2.0) y -= 2.0;
+  return 0.5 * (y >= 1.0 ? y - 2.0 : y);
+}
+
 // phase (cycles, before that block's phase_adjust) and step frequency at the start of block `job`
 static inline void fine_state_at(const FineHost& h, unsigned job, int olen, int V, double* phase, double* feff) {
   const unsigned kbu = job - h.job0;
@@ -52,8 +65,8 @@ static inline void fine_retune(FineHost& h, unsigned job, int olen, int V, int s
   double cur_rate = h.rate;
   // set_osc (src/osc.c:28-47): a fresh oscillator starts at phasor 1, freq 0, rate 0
   if (!h.osc_init) { phase = 0.0; feff = 0.0; cur_rate = 0.0; h.set_freq = 0.0; h.set_rate = 0.0; h.osc_init = true; }
-  if (freq != h.set_freq) { h.set_freq = freq; feff = freq; }
-  if (rate != h.set_rate) { h.set_rate = rate; cur_rate = rate; }
+  if (freq != h.set_freq) { h.set_freq = freq; feff = osc_step_cycles(freq); }
+  if (rate != h.set_rate) { h.set_rate = rate; cur_rate = osc_step_cycles(rate); }
   int adj = h.adj_num;
   if (shift != h.bin_shift) {                                           // src/radio.c:1491-1496
     adj = ((shift % V) + V) % V;                                        // cispi(2*(shift % V)/V): whole turns drop out

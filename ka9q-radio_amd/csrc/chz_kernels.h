@@ -3373,6 +3373,18 @@ __device__ __forceinline__ float2* mini_fft(float2* a, float2* b, const MiniPara
   return a;        // where the result is
 }
 
+// ISB unpacking of a slave's P gathered bins in LDS (src/filter.c:895-909): bin 0 zeroed, pairs p = 1 .. P/2 - 1 -- the reference
+// loops p < s_bins/2, so an odd P = 2h + 1 leaves its innermost pair (h, h + 1) alone.  Shared by mini_gather and rmini_slave.
+__device__ __forceinline__ void mini_isb_unpack(float2* Y, int P, int tid, int nthr) {
+  for (int q = tid; q < P / 2; q += nthr) {
+    if (q == 0) { Y[0] = make_float2(0.f, 0.f); continue; }
+    const float2 pos = Y[q], neg = Y[P - q];
+    Y[q] = make_float2(pos.x + neg.x, pos.y - neg.y);          // pos + conj(neg)
+    Y[P - q] = make_float2(neg.x - pos.x, neg.y + pos.y);      // neg - conj(pos)
+  }
+  __syncthreads();
+}
+
 // gather x response into the slave's bins (FFT order), exactly as chan_ifft does for a COMPLEX master, ISB unpacking
 // (src/filter.c:895-909) and the zeroed Nyquist bin (:911, after the unpack): X[P] -> Y[P], H the slave's response
 __device__ __forceinline__ void mini_gather(const float2* X, float2* Y, const float2* __restrict__ H, const ChanDesc& d, int isb, int P,
@@ -3388,16 +3400,7 @@ __device__ __forceinline__ void mini_gather(const float2* X, float2* Y, const fl
     Y[i] = v;
   }
   __syncthreads();
-  if (isb) {                                               // src/filter.c:895-909
-    for (int q = tid; q <= P / 2; q += nthr) {
-      if (q == 0) { Y[0] = make_float2(0.f, 0.f); continue; }
-      if (2 * q >= P) continue;
-      const float2 pos = Y[q], neg = Y[P - q];
-      Y[q] = make_float2(pos.x + neg.x, pos.y - neg.y);          // pos + conj(neg)
-      Y[P - q] = make_float2(neg.x - pos.x, neg.y + pos.y);      // neg - conj(pos)
-    }
-    __syncthreads();
-  }
+  if (isb) mini_isb_unpack(Y, P, tid, nthr);
   if (tid == 0) Y[(P + 1) / 2] = make_float2(0.f, 0.f);     // :911 comes after the unpack
   __syncthreads();
 }
@@ -3670,15 +3673,7 @@ __device__ __forceinline__ const float2* rmini_slave(const float2* S, float2* Y,
       Y[i] = v;
     }
     __syncthreads();
-    if (isb) {                                                             // src/filter.c:895-909: pairs p = 1 .. s_bins/2 - 1 (an odd P leaves its innermost pair alone)
-      for (int q = tid; q < P / 2; q += nthr) {
-        if (q == 0) { Y[0] = make_float2(0.f, 0.f); continue; }
-        const float2 pos = Y[q], neg = Y[P - q];
-        Y[q] = make_float2(pos.x + neg.x, pos.y - neg.y);                  // pos + conj(neg)
-        Y[P - q] = make_float2(neg.x - pos.x, neg.y + pos.y);              // neg - conj(pos)
-      }
-      __syncthreads();
-    }
+    if (isb) mini_isb_unpack(Y, P, tid, nthr);
     if (tid == 0) Y[(P + 1) / 2] = make_float2(0.f, 0.f);                  // :911 comes after the unpack
   } else {
     const int SB = P / 2 + 1;

@@ -477,6 +477,40 @@ def test_dropin_filter2_inline_masters(blocking, isb_ch):
 
 
 @pytest.mark.gpu
+def test_dropin_odd_inline_master_with_isb(tmp_path):
+    """create_filter_input(135, 109, COMPLEX) with a same-size COMPLEX slave and slave->isb set (tests/c/mini_odd_harness.c): N = 243 =
+    3^5, an odd pooled inline master, where the reference's ISB unpack (src/filter.c:899, p < s_bins/2) leaves the innermost pair of bins
+    alone.  The filter passes everything up to both Nyquist bins, which is where a wrong bound shows.  Three blocks, one of them with a
+    shift, against the restated overlap-save pair; the master must have created no engine."""
+    _build_lib(); ol.build()
+    L, M, nblocks = 135, 109, 3
+    N = L + M - 1
+    lo, hi, beta, shifts = -0.5, 0.5, 3.0, [0, 1, 60]
+    rng = np.random.default_rng(243)
+    x = (rng.standard_normal(nblocks * L) + 1j * rng.standard_normal(nblocks * L)).astype(np.complex64)
+    x.tofile(str(tmp_path / "in.bin"))
+    exe = str(tmp_path / "mini_odd_harness")
+    subprocess.run(["gcc", "-O2", "-std=gnu11", "-Wall", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "c", "mini_odd_harness.c"), "-o", exe,
+                    "-L", LIBDIR, "-lka9q_filter_hip", "-lchz_hip", "-Wl,-rpath," + LIBDIR, "-lpthread", "-lm"], check=True)
+    r = subprocess.run([exe, str(tmp_path), str(L), str(M), str(nblocks), "1", repr(lo), repr(hi), repr(beta)] + [str(s) for s in shifts],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.split() == ["engines", "0", "inline", "1", "points", str(N), "bins", str(N)], r.stdout     # a pooled inline master, not an engine
+    out = np.fromfile(str(tmp_path / "out.bin"), np.complex64).reshape(nblocks, L)
+    resp = ol.set_filter(N, L, N, False, lo, hi, beta)
+    h = N // 2
+    assert min(abs(resp[h]), abs(resp[h + 1])) > 0.5 * np.abs(resp).max()        # the innermost pair carries signal
+    st = ol.Stream(L, M, ol.COMPLEX)
+    for b in range(nblocks):
+        s64 = st.push(x[b * L:(b + 1) * L], f64=True)
+        want = ol.channel(s64, ol.COMPLEX, N, L, shifts[b], resp, isb=True)
+        err = float(np.sqrt(np.mean(np.abs(out[b] - want) ** 2)))
+        rms = float(np.sqrt(np.mean(np.abs(want) ** 2)))
+        assert rms > 0 and err <= 1e-5 * rms + 2e-8 * float(np.abs(s64).max()) * float(np.linalg.norm(resp)), (b, err, rms)
+        print("block %d shift %d: rel error %.3g" % (b, shifts[b], err / rms))
+
+
+@pytest.mark.gpu
 def test_dropin_channels_retuning_every_block():
     # 1/5 of the channels change their bin shift EVERY block (scanning receivers, Doppler tracking): each of them misses
     # the speculative batch, the misses of one block are served together, nothing drains the pipeline, every output is exact

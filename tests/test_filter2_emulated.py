@@ -1,6 +1,6 @@
 """CPU-tier twin of tests/test_gpu_filter2.py: the engine's host code and the unmodified f2_ovs kernel built for the CPU
 (tests/test_engine_emulated.py) run that whole file in a child process -- the blocking-1 chain next to a plain bank, blocking 4 and 3
-with their pending blocks, the FM bank, the odd size, blocks in flight against blocks stepped, the mid-stream edits, the grid edges and
+with their pending blocks, the FM bank, the odd size, the two odd transform lengths with ISB (N2 = 243, 729), blocks in flight against blocks stepped, the mid-stream edits, the grid edges and
 the refusals."""
 import os
 import re
@@ -17,4 +17,4 @@ def test_filter2_stage_on_the_emulator(emulated_engine):
     tail = r.stdout.strip().splitlines()[-1] if r.stdout.strip() else ""
     assert r.returncode == 0, (tail, r.stdout[-3000:], r.stderr[-1500:])
     m = re.search(r"(\d+) passed", tail)
-    assert m and int(m.group(1)) == 10 and "skipped" not in tail and "deselected" not in tail, tail
+    assert m and int(m.group(1)) == 12 and "skipped" not in tail and "deselected" not in tail, tail

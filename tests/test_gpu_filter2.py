@@ -102,6 +102,7 @@ class Chain:
         self.last_pcm = {}
         self.fired = 0
         self.frames = 0           # data frames held against the oracle's PCM
+        self.worst = 0.0          # largest relative L2 error of a filter2 output so far
 
     def reset(self, job, ch0, n):
         self.bank.filter2_reset(job, ch0, n)
@@ -146,6 +147,7 @@ class Chain:
             else:
                 want = ol.channel(self.streams[i].push(x, f64=True), ol.COMPLEX, self.N2, self.L2, 0, self.resp2[i], isb=bool(self.isb[i]))
                 err = np.linalg.norm(filt[i] - want) / max(np.linalg.norm(want), 1e-12)
+                self.worst = max(self.worst, err)
                 assert err <= 3e-6, (b, i, err)
                 assert np.linalg.norm(want) > 0
             assert power[i] == pytest.approx(np.mean(np.abs(filt[i].astype(np.complex128)) ** 2), rel=1e-6, abs=1e-300), (b, i)
@@ -269,6 +271,29 @@ def test_an_odd_size_runs_radix_3_and_5(pkg):
         for b in range(6):
             eng.write(x[b * L:(b + 1) * L]); eng.step(b)
             ch.block(b)
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("B,M2,geom,nblk", [(1, 4, (240, 4, 243), 6), (3, 10, (720, 10, 729), 9)])
+def test_an_odd_length_with_isb(pkg, B, M2, geom, nblk):
+    """N2 = 243 = 3^5 (B = 1) and N2 = 729 = 3^6 (B = 3, with its pending blocks): an explicit M2 makes the filter2 transform odd, where
+    the ISB unpack leaves the innermost pair (h, h + 1) of N2 = 2h + 1 alone (src/filter.c:899).  Three channels, the middle one ISB; the
+    responses reach the Nyquist bins -- all-pass Kaiser on channel 0, random on the other two -- because that pair is where a wrong
+    bound shows.  Filter output only."""
+    x = am_signal(nblk)
+    rng = np.random.default_rng(geom[2])
+    eng = pkg.engine.Engine(L, M, ol.REAL, ring_blocks=8)
+    try:
+        bank = first_bank(pkg, eng, 3)
+        rnd = (rng.standard_normal((2, geom[2])) + 1j * rng.standard_normal((2, geom[2]))).astype(np.complex64)
+        ch = Chain(pkg, eng, bank, B, M2, [ol.set_filter(geom[2], geom[0], geom[2], False, -0.5, 0.5, 3.0), rnd[0], rnd[1]], isb=[0, 1, 0])
+        assert (ch.L2, ch.M2, ch.N2) == geom and ch.N2 % 2 == 1
+        for b in range(nblk):
+            eng.write(x[b * L:(b + 1) * L]); eng.step(b)
+            ch.block(b)
+        assert ch.fired == nblk // B
+        print("N2 %d: worst rel-L2 %.3g, %.3g of the bound" % (ch.N2, ch.worst, ch.worst / 3e-6))
     finally:
         eng.close()
 

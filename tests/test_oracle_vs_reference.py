@@ -126,6 +126,32 @@ def test_isb_unpack_matches_reference(oracle_built):
         m.close()
 
 
+@pytest.mark.parametrize("L,M", [(135, 109), (6, 4)])          # N = 243 = 3^5 and N = 9: odd inline masters
+def test_isb_unpack_on_an_odd_complex_master_matches_reference(oracle_built, L, M):
+    """A COMPLEX master of odd N = 2h + 1 with a same-size ISB slave: the reference's unpack loops p < s_bins/2 (src/filter.c:899), so the
+    innermost pair (h, h + 1) stays as gathered.  Shift -1 is pinned too: with an odd master `rp != (m_bins+1)/2` (the gather's loop
+    condition) ends the loop after one bin and the whole output is zero -- in the reference and in the restatement alike."""
+    N = L + M - 1
+    assert N % 2 == 1
+    m = ol.RefMaster(L, M, ol.COMPLEX)
+    try:
+        c = m.channel(L, ol.COMPLEX)
+        assert c.points == N
+        resp = (rng.standard_normal(N) + 1j * rng.standard_normal(N)).astype(np.complex64)
+        c.set_response(resp)
+        c.set_isb(True)
+        x = (rng.standard_normal(L) + 1j * rng.standard_normal(L)).astype(np.complex64)
+        m.write(x)
+        spec = m.spectrum()
+        for s in [0, 1, -1, N // 4]:
+            out_ref = c.execute(s)
+            out = ol.channel(spec, ol.COMPLEX, N, L, s, resp, isb=True)
+            assert np.abs(out - out_ref).max() <= 2e-6 * np.abs(out_ref).max(), s
+            assert out_ref.any() == (s != -1), s
+    finally:
+        m.close()
+
+
 def test_notch_matches_reference(oracle_built):
     L, M = 25920, 6481
     m = ol.RefMaster(L, M, ol.REAL)
