@@ -13,7 +13,7 @@ f32=True runs the same statements on the oracle's float32 transform: the "f32 tw
 its own arithmetic rounds differently.
 
 Also here: the AFSK signal generator (CRC, bit stuffing, NRZI, continuous phase, idle flags, a gain on the space tone, a start offset
-inside a bit) and the reference's input feeder (five blocks of zeros after a block that ends in 100 zero samples, :540-546)."""
+inside a bit, any ratio of sample rate to bit rate) and the reference's input feeder (five blocks of zeros after a block that ends in 100 zero samples, :540-546)."""
 import math
 
 import numpy as np
@@ -211,16 +211,24 @@ def line_bits(items):
 
 
 def modulate(bits, samprate, bitrate=BITRATE, mark=MARK, space=SPACE, amplitude=0.5, space_gain=1.0, offset=0, phase=0.0):
-    """NRZI (a zero toggles the tone), continuous phase, samprate / bitrate samples a bit (an integer here); the first `offset` samples are
-    dropped, so the block grid starts inside a bit.  -> int16 values"""
-    sps = int(round(samprate / bitrate))
-    assert sps * bitrate == samprate
+    """NRZI (a zero toggles the tone), continuous phase, a true baud clock: sample n carries line bit floor(n bitrate / samprate), so samprate /
+    bitrate need not be an integer (where it is, every bit has exactly that many samples); the first `offset` samples are dropped, so the block
+    grid starts inside a bit.  -> int16 values"""
     tone, level = [], 0                         # level 0 = mark
     for b in bits:
         if not b:
             level ^= 1
         tone.append(level)
-    tone = np.repeat(np.asarray(tone, np.int8), sps)
+    tone = np.asarray(tone, np.int8)
+    # the first sample of bit k is ceil(k samprate / bitrate): bit k's samples are those n with k <= n bitrate / samprate < k + 1.  Integer arithmetic
+    # where the rates are whole numbers of Hz (every rate here), so that no sample falls on the wrong side of a bit edge by a rounding
+    fs, br = float(samprate), float(bitrate)
+    k = np.arange(tone.size + 1, dtype=np.int64)
+    if fs.is_integer() and br.is_integer():
+        first = -((-k * int(fs)) // int(br))
+    else:
+        first = np.ceil(k * (fs / br)).astype(np.int64)
+    tone = np.repeat(tone, np.diff(first))
     freq = np.where(tone == 0, mark, space)
     ph = phase + 2 * np.pi * np.cumsum(freq) / samprate
     x = amplitude * np.where(tone == 0, 1.0, space_gain) * np.sin(ph)
@@ -249,9 +257,9 @@ def feed(x, L):
     return np.stack(out)
 
 
-def run(blocks, L, M, samprate, f32=False):
+def run(blocks, L, M, samprate, f32=False, bitrate=BITRATE, mark=MARK, space=SPACE):
     """a fresh Decoder over int16 blocks -> the list of block records"""
-    d = Decoder(L, M, samprate, f32=f32)
+    d = Decoder(L, M, samprate, bitrate=bitrate, mark=mark, space=space, f32=f32)
     return [d.block(to_float(b)) for b in blocks]
 
 

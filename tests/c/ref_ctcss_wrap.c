@@ -1,9 +1,10 @@
 // ref_ctcss_wrap.c -- TEST INFRASTRUCTURE: the reference's ctcss.c, included unmodified where it lies (never copied).  ctcss's processing is
 // the body of its main(), so main is renamed and the three calls that reach the network -- setup_mcast_in(), select() and recvfrom() -- are
-// redirected to a feeder that makes RTP packets from a file of samples; after every tenth packet (one 200 ms block) the feeder records what the
+// redirected to a feeder that makes RTP packets from a file of samples; after every block's last packet (ten a block, or as many as the caller names:
+// the packet size must divide L = lrint(0.2 samprate), and ten does not divide 2205) the feeder records what the
 // session holds, and when the file ends it leaves through exit().  tests/test_ctcss_reference.py builds this as a program in its tmp_path
 // together with the reference's filter.c ... rtp.c and the oracle's FFT provider.
-//   ref_ctcss <samples.s16be> <samprate> <f32: 0 | 1> <records.txt>
+//   ref_ctcss <samples.s16be> <samprate> <f32: 0 | 1> <records.txt> [packets per block, default 10]
 #include <sys/types.h>
 #include <sys/socket.h>
 #include <sys/select.h>
@@ -52,21 +53,21 @@ int address_match(void const *a, void const *b) { (void)a; (void)b; return 1; }
 void oracle_fft_set_precision(int f32);
 
 static FILE *In, *Out;
-static int Samprate, Per_packet, Type;
+static int Samprate, Per_packet, Type, Per_block = 10;
 static long Packets;
 static uint16_t Seq;
 static uint32_t Timestamp;
 
-// before every packet: after each tenth one the session has just finished a block (put_rfilter() completed on the packet's last sample)
+// before every packet: after each block's last one the session has just finished a block (put_rfilter() completed on the packet's last sample)
 static int refctcss_select(fd_set *readfds) {
-  if (Packets > 0 && Packets % 10 == 0 && Sessions)
+  if (Packets > 0 && Packets % Per_block == 0 && Sessions)
     fprintf(Out, "%d %.17g %.17g\n", Sessions->strongest_tone_index, Sessions->strongest_tone_energy, Sessions->current_pl_tone);
-  if (Packets % 10 == 0) {                          // leave at a block edge when less than a whole block is left
+  if (Packets % Per_block == 0) {                          // leave at a block edge when less than a whole block is left
     const long at = ftell(In);
     fseek(In, 0, SEEK_END);
     const long left = ftell(In) - at;
     fseek(In, at, SEEK_SET);
-    if (left < 10L * Per_packet * (long)sizeof(int16_t)) { fclose(Out); exit(0); }
+    if (left < (long)Per_block * Per_packet * (long)sizeof(int16_t)) { fclose(Out); exit(0); }
   }
   FD_ZERO(readfds);
   FD_SET(REFCTCSS_FD, readfds);
@@ -88,13 +89,16 @@ static ssize_t refctcss_recvfrom(void *buf, size_t len, struct sockaddr *from, s
 }
 
 int main(int argc, char *argv[]) {
-  if (argc != 5) return 2;
+  if (argc != 5 && argc != 6) return 2;
   In = fopen(argv[1], "rb");
   Samprate = atoi(argv[2]);
   oracle_fft_set_precision(atoi(argv[3]));
   Out = fopen(argv[4], "w");
   if (!In || !Out || Samprate <= 0) return 2;
-  Per_packet = (int)lrint(Filter_time * Samprate) / 10;          // a tenth of a block: 480 samples at 24 kHz, as a 20 ms packet carries
+  if (argc == 6) Per_block = atoi(argv[5]);
+  const int block = (int)lrint(Filter_time * Samprate);
+  if (Per_block < 1 || block % Per_block) return 2;
+  Per_packet = block / Per_block;                                // a tenth of a block by default: 480 samples at 24 kHz, as a 20 ms packet carries
   Type = pt_from_info(Samprate, 1, S16BE);
   if (Type < 0) return 2;
   // the reference's FFT runs in the caller's thread: with filter.c's worker thread the first block of a master is gathered without waiting for

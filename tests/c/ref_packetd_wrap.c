@@ -47,6 +47,10 @@ static ssize_t refpkt_capture(const void *buf, size_t len) {
 #undef send
 #undef main
 
+// Bitrate is a plain file static of packetd.c (:54, 1200 unless main() parsed another): set it before a task starts.  samppbit and the filter's
+// edges follow it (:496-497,509); the tones are const (:481-482).
+__attribute__((visibility("default"))) void refpkt_set_bitrate(double bitrate) { Bitrate = bitrate; }
+
 // decode_task() over the file `path` (big-endian 16-bit samples, as ntohs() at :551 reads them) for a session of `samprate`: the packets it
 // "sends" (RTP header and frame) land in out[0, out_size) one behind the other, their lengths in lens[0, max_packets); returns their number.
 // decode_task declares its struct filter_out uninitialised and create_filter_output() reads `init` from it, so the task runs on a thread

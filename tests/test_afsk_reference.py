@@ -23,6 +23,7 @@ import pytest
 import afsk_oracle as ao
 import oracle_lib as ol
 import test_gpu_afsk as tg
+import test_gpu_afsk_rates            # noqa: F401  (registers its shapes with test_gpu_afsk)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE = os.path.join(ROOT, "oracle")
@@ -56,17 +57,21 @@ def refpkt(tmp_path_factory):
     L = C.CDLL(lib)
     L.refpkt_run.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_int]
     L.oracle_fft_set_precision.argtypes = [C.c_int]
+    L.refpkt_set_bitrate.argtypes = [C.c_double]
+    L.refpkt_set_bitrate.restype = None
     return L
 
 
-def reference_frames(refpkt, path, samprate, f32):
+def reference_frames(refpkt, path, samprate, f32, bitrate=ao.BITRATE):
     out = np.zeros(1 << 16, np.uint8)
     lens = np.zeros(64, np.int32)
     refpkt.oracle_fft_set_precision(int(f32))
+    refpkt.refpkt_set_bitrate(bitrate)
     try:
         n = refpkt.refpkt_run(path.encode(), int(samprate), out.ctypes.data, out.size, lens.ctypes.data, lens.size)
     finally:
         refpkt.oracle_fft_set_precision(0)
+        refpkt.refpkt_set_bitrate(ao.BITRATE)
     assert 0 <= n <= lens.size, n
     at, frames = 0, []
     for k in range(n):
@@ -91,6 +96,33 @@ def test_the_restatement_s_frames_equal_the_reference_s(refpkt, tmp_path, shape)
             ref = reference_frames(refpkt, path, fs, f32)
             assert ref == mine, (shape, k, "float32 transform" if f32 else "float64 transform", [len(f) for f in ref], [len(f) for f in mine])
         print("%s instance %d: %d frames equal on both transforms; FLOOR %.3g, smallest margins %.3g / %.3g" % (shape, k, len(mine), floor, m1, m2))
+
+
+@needs_ref
+@pytest.mark.parametrize("shape", ["22k", "22k1225", "ref300"])
+def test_the_restatement_s_frames_equal_the_reference_s_where_a_bit_is_no_whole_number_of_samples(refpkt, tmp_path, shape):
+    """tests/test_gpu_afsk_rates.py's scenario (frames of 1, 17, 64 and 330 payload bytes, equal tones and the space tone 1.8 x the mark tone) at
+    22050 / 1200 (samppbit 18 of 18.375: the reference's clock slips, and the restatement must lose the same frames in the same order), at 22050 /
+    1225 (exactly 18: the control, all four frames) and at 16000 / 300 (53 of 53.33) with the tones packetd.c fixes; the wrapper sets packetd.c's
+    file static Bitrate before the task starts.  The other shapes of that file (tones of 1600 / 1800 Hz, L 480, M - 1 != L: packetd.c's tones are
+    const and its AL / AM fixed) rest on the restatement's parametrisation.
+    Measured: 22k delivers the frames of [1, 17] payload bytes with one CRC failure at equal tones and [17, 64, 330] with the space tone raised;
+    22k1225 delivers all four; ref300 (53 of 53.33 samples a bit, a clock that runs 0.6 % fast over frames of up to 2700 bits) delivers [1, 64] with
+    five CRC failures at equal tones and [17, 64, 330] with the space tone raised -- the reference loses the same ones; FLOOR 0.8e-5 to 1.3e-5."""
+    L, M, fs, br, mk, sp = tg.geom(shape)
+    assert (L, M, mk, sp) == (960, 961, 1200.0, 2200.0)      # AL, AM, mark_tone, space_tone of src/packetd.c
+    blocks, want = tg.scenario(shape)
+    for k in (0, 1):
+        floor, m1, m2, _ = tg.input_condition(shape, k)
+        mine, twin = ao.frames_of(tg.restatement(shape, False)[k]), ao.frames_of(tg.restatement(shape, True)[k])
+        assert twin == mine and len(mine) >= 1 and all(f in want[k] for f in mine), (shape, k, [len(f) for f in mine])
+        assert (mine == want[k]) == (shape == "22k1225"), (shape, k, [len(f) for f in mine])
+        path = str(tmp_path / ("inst%d.s16be" % k))
+        ao.to_wire(blocks[k].reshape(-1), big_endian=True).tofile(path)
+        for f32 in (False, True):
+            ref = reference_frames(refpkt, path, fs, f32, bitrate=br)
+            assert ref == mine, (shape, k, "float32 transform" if f32 else "float64 transform", [len(f) for f in ref], [len(f) for f in mine])
+        print("%s instance %d: frames of %s bytes, equal on both transforms; FLOOR %.3g, smallest margins %.3g / %.3g" % (shape, k, [len(f) for f in mine], floor, m1, m2))
 
 
 @needs_ref

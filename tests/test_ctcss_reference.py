@@ -7,7 +7,8 @@ program with the reference's release flags (oracle/Makefile's REF_CFLAGS) togeth
 osc gauss rtp and the oracle's FFT provider (oracle/_build/fftw_shim.o, dft_ref.o); the reference's transform runs in the caller's thread
 (N_worker_threads = 0, for the reason tests/c/ref_packetd_wrap.c gives).
 
-Input: instance 0 of tests/test_gpu_ctcss.py's scenario at 24 and 8 kHz, on the reference's float64 transform and on its float32 one
+Input: instance 0 of tests/test_gpu_ctcss.py's scenario at 24 and 8 kHz and at the five rates of tests/test_gpu_ctcss_rates.py (11025, 22050, 40960,
+16000 and 9999 Hz; the feeder is told how many packets make a block where ten do not divide it), on the reference's float64 transform and on its float32 one
 (oracle_fft_set_precision).  On every block the restatement's index and sticky tone equal the reference's, and the energy is within the
 device rule of tests/test_gpu_ctcss.py: 1e-6 relative to the block's largest energy, or 4 x the f32 twin's own distance on that block where
 that is larger (the reference's float32 transform is compared with the restatement's float64 run, like a device).  The input condition of
@@ -23,6 +24,7 @@ import afsk_oracle as ao
 import ctcss_oracle as co
 import oracle_lib as ol
 import test_gpu_ctcss as tg
+import test_gpu_ctcss_rates as tr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE = os.path.join(ROOT, "oracle")
@@ -54,25 +56,33 @@ def refctcss(tmp_path_factory):
     return prog
 
 
-def reference_records(prog, path, samprate, f32, out):
-    r = subprocess.run([prog, path, str(int(samprate)), str(int(f32)), out], capture_output=True, text=True, timeout=300)
+def reference_records(prog, path, samprate, f32, out, per_block=10):
+    r = subprocess.run([prog, path, str(int(samprate)), str(int(f32)), out, str(per_block)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.returncode, r.stderr[-1500:])
     with open(out) as f:
         rows = [line.split() for line in f]
     return [(int(a), float(b), float(c)) for a, b, c in rows]
 
 
+# the rates of tests/test_gpu_ctcss_rates.py: (rate, packets a block).  The feeder's packet must divide L: ten does not divide 2205 (nine packets of
+# 245 samples do), and a sixteenth of 8192 is 512 samples, 1024 bytes, inside the reference's packet buffer
+RATES = {"11k": 9, "22k": 10, "41k": 16, "16k": 10, "9999": 10}
+
+
 @needs_ref
-@pytest.mark.parametrize("shape", list(tg.SHAPES))
+@pytest.mark.parametrize("shape", list(tg.SHAPES) + list(RATES))
 def test_the_restatement_s_decisions_equal_the_reference_s(refctcss, tmp_path, shape):
-    fs = tg.SHAPES[shape]
-    blocks = tg.scenario(shape)[0]
-    mine, twin = tg.restatement(shape, False)[0], tg.restatement(shape, True)[0]
+    if shape in RATES:
+        fs, per_block = tr.RATES[shape][0], RATES[shape]
+        blocks, mine, twin = tr.scenario(shape)[0], tr.restatement(shape, False)[0], tr.restatement(shape, True)[0]
+    else:
+        fs, per_block = tg.SHAPES[shape], 10
+        blocks, mine, twin = tg.scenario(shape)[0], tg.restatement(shape, False)[0], tg.restatement(shape, True)[0]
     floor, smallest, where = tg.input_condition(mine, twin, shape)
     path = str(tmp_path / "inst0.s16be")
     ao.to_wire(blocks.reshape(-1), big_endian=True).tofile(path)
     for f32 in (False, True):
-        ref = reference_records(refctcss, path, fs, f32, str(tmp_path / ("records%d.txt" % f32)))
+        ref = reference_records(refctcss, path, fs, f32, str(tmp_path / ("records%d.txt" % f32)), per_block)
         assert len(ref) == len(mine) == 175
         worst = 0.0
         for blk, ((index, energy, current), r, t) in enumerate(zip(ref, mine, twin)):

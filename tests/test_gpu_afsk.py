@@ -63,6 +63,19 @@ LEAD = 30
 # restatement alone, so that every decision carries its margin and -- at 24 kHz -- both frames of the pair complete in one block
 OFFSET1 = {"48k": 22, "24k": 10, "12k": 7}
 PAIR_FLAGS = {"48k": 3, "24k": 3, "12k": 3}
+# shapes of other test files (tests/test_gpu_afsk_rates.py), which run this file's helpers at rates and tones of their own:
+# name -> ((L, M, samprate, bitrate, mark, space), a function that returns what scenario() returns for it)
+EXTRA = {}
+
+
+def register(name, geom6, make_scenario):
+    assert name not in SHAPES and len(geom6) == 6
+    EXTRA[name] = (tuple(geom6), make_scenario)
+
+
+def geom(shape):
+    """(L, M, samprate, bitrate, mark, space) of a shape: packetd's own rates and tones for the shapes of this file"""
+    return EXTRA[shape][0] if shape in EXTRA else SHAPES[shape] + (ao.BITRATE, ao.MARK, ao.SPACE)
 
 
 @pytest.fixture(scope="module")
@@ -114,6 +127,8 @@ def decodes_from_every_clock_phase(shape):
 @functools.lru_cache(maxsize=None)
 def scenario(shape):
     """int16 blocks [nblocks][L] of instances 0-3 and the frames each must deliver"""
+    if shape in EXTRA:
+        return EXTRA[shape][1]()
     L, M, fs = SHAPES[shape]
     sps = int(fs / ao.BITRATE)
     pl = payloads(11, (1, 17, 64, 330))
@@ -140,8 +155,8 @@ def scenario(shape):
 
 @functools.lru_cache(maxsize=None)
 def restatement(shape, f32):
-    L, M, fs = SHAPES[shape]
-    return [ao.run(b, L, M, fs, f32=f32) for b in scenario(shape)[0]]
+    L, M, fs, br, mk, sp = geom(shape)
+    return [ao.run(b, L, M, fs, f32=f32, bitrate=br, mark=mk, space=sp) for b in scenario(shape)[0]]
 
 
 def status_dict(s):
@@ -192,15 +207,15 @@ def buffers(n):
 
 def run_pool(pkg, shape, cap, seed=7, big_endian=True, only=None):
     """the scenario through a pool of capacity `cap`: [inst] -> list over blocks of (status dict, raw status bytes, frames)"""
-    L, M, fs = SHAPES[shape]
+    L, M, fs, br, mk, sp = geom(shape)
     E = pkg.engine
     blocks = scenario(shape)[0]
-    src = {0: blocks[0], 1: blocks[1], 2: blocks[2], 3: blocks[3], 4: blocks[0]}
     ks = list(range(NINST)) if only is None else list(only)
-    pool = E.AfskPool(L, M, fs, cap, byte_order=E.AFSK_BE if big_endian else E.AFSK_LE, frame_stride=STRIDE)
+    src = {k: blocks[0 if k == 4 else k] for k in ks}
+    pool = E.AfskPool(L, M, fs, cap, bitrate=br, mark=mk, space=sp, byte_order=E.AFSK_BE if big_endian else E.AFSK_LE, frame_stride=STRIDE)
     dev = None
     try:
-        resp = ao.response(L, M, fs)
+        resp = ao.response(L, M, fs, br, mk, sp)
         inst = {k: pool.add() for k in ks}
         for k in ks:
             pool.set_response(inst[k], resp)
@@ -238,13 +253,13 @@ def device_run(pkg, shape):
 
 
 def startup(shape):
-    L, M, fs = SHAPES[shape]
-    return (M - 1) // 2 + int(fs / ao.BITRATE)
+    L, M, fs, br = geom(shape)[:4]
+    return (M - 1) // 2 + int(fs / br)
 
 
 def input_condition(shape, k):
     """the margins of strict instance k (see the module's docstring) -> (floor, smallest first margin, smallest second margin, largest |cur_val|)"""
-    L = SHAPES[shape][0]
+    L = geom(shape)[0]
     ref, twin = restatement(shape, False)[k], restatement(shape, True)[k]
     cur = np.array([c for r in ref for c in r["cur"]]); tcur = np.array([c for r in twin for c in r["cur"]])
     assert cur.shape == tcur.shape, (shape, k, "the f32 twin takes another number of decisions: unusable input")
@@ -268,7 +283,9 @@ def input_condition(shape, k):
 CANCELLING = 0.25          # a difference below this share of its terms is held to the rule relative to the terms (see the docstring)
 
 
-def check_strict(shape, k, got, kref=None):
+def check_strict(shape, k, got, kref=None, last_val_may_cancel=False):
+    """last_val_may_cancel: an input whose clock slips takes decisions near bit edges, where last_val cancels too (this file's inputs never do,
+    and that is asserted); last_val is then held to the rule relative to ITSELF all the same -- the cancellation rule stays mid_val's alone"""
     kref = k if kref is None else kref
     floor, m1, m2, top = input_condition(shape, kref)
     ref, twin = restatement(shape, False)[kref], restatement(shape, True)[kref]
@@ -285,13 +302,16 @@ def check_strict(shape, k, got, kref=None):
                 continue
             scale = abs(r[f])
             if scale < CANCELLING * terms:
-                scale = terms; cancelling[f] += 1
+                cancelling[f] += 1
+                if f == "mid_val" or not last_val_may_cancel:
+                    scale = terms
             e, lim = abs(st[f] - r[f]) / scale, max(1e-6, 4 * abs(t[f] - r[f]) / scale)
             worst[f] = max(worst[f], e / lim)
             assert e <= lim, (shape, k, blk, f, st[f], r[f], e, lim)
-    assert cancelling["last_val"] == 0
-    print("%s instance %d: FLOOR %.3g, smallest margins %.3g / %.3g; worst measured / allowed: last_val %.2f, mid_val %.2f (%d of %d blocks relative to the terms)"
-          % (shape, k, floor, m1, m2, worst["last_val"], worst["mid_val"], cancelling["mid_val"], len(ref)))
+    assert last_val_may_cancel or cancelling["last_val"] == 0
+    print("%s instance %d: FLOOR %.3g, smallest margins %.3g / %.3g; worst measured / allowed: last_val %.2f, mid_val %.2f (%d of %d blocks relative to the terms)%s"
+          % (shape, k, floor, m1, m2, worst["last_val"], worst["mid_val"], cancelling["mid_val"], len(ref),
+             "; last_val below a quarter of its terms on %d blocks, held relative to itself" % cancelling["last_val"] if cancelling["last_val"] else ""))
 
 
 @pytest.mark.parametrize("shape", list(SHAPES))

@@ -68,7 +68,7 @@ def instance2(fs):
     half = int(fs / 200)                                                    # half a period of 100 Hz
     sq = np.where((np.arange(3 * L) // half) % 2 == 0, 32767, -32768).astype(np.int16).reshape(3, L)
     late = co.generate(fs, [(4, [(136.5, 0.3)], 0.0)])
-    late = np.concatenate([np.zeros(L // 2, np.int16), late.reshape(-1)[:3 * L + L // 2]]).reshape(4, L)      # the tone starts mid-block
+    late = np.concatenate([np.zeros(L // 2, np.int16), late.reshape(-1)[:4 * L - L // 2]]).reshape(4, L)      # the tone starts mid-block (an odd L: one sample before the middle)
     return np.concatenate([sq, np.zeros((3, L), np.int16), late, np.zeros((2, L), np.int16)])
 
 

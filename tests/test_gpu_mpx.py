@@ -65,15 +65,20 @@ def pkg():
     return p
 
 
+def block_time(shape):
+    """a shape is one of SHAPES' names, or (tests/test_gpu_mpx_shapes.py) a block time in seconds"""
+    return SHAPES[shape] if isinstance(shape, str) else shape
+
+
 @functools.lru_cache(maxsize=None)
 def scenario(shape):
     """int16 blocks [NBLOCKS][L] per instance"""
-    return [mo.signal(NBLOCKS, SHAPES[shape], k, a, script) for k, (a, _, script) in enumerate(SCENARIO)]
+    return [mo.signal(NBLOCKS, block_time(shape), k, a, script) for k, (a, _, script) in enumerate(SCENARIO)]
 
 
 @functools.lru_cache(maxsize=None)
 def restatement(shape, f32):
-    return [mo.run(b, SHAPES[shape], rate=SCENARIO[k][1], f32=f32) for k, b in enumerate(scenario(shape))]
+    return [mo.run(b, block_time(shape), rate=SCENARIO[k][1], f32=f32) for k, b in enumerate(scenario(shape))]
 
 
 def whole_window_signal(script, nblocks):
@@ -136,7 +141,7 @@ def one_block(pool, inst, row, audio=True):
 def run_pool(pkg, shape, cap, src, params, kind=mo.STEREO, big_endian=True, on_device=False, audio=True, seed=7):
     """src: {k: int16 blocks}, params: {k: (rate, gain)} -> {k: list over blocks of (pcm bytes, audio floats or None, status tuple)}"""
     E = pkg.engine
-    bt = SHAPES[shape]
+    bt = block_time(shape)
     ks = list(src)
     pool = E.MpxPool(bt, cap, kind=kind, byte_order=E.MPX_BE if big_endian else E.MPX_LE)
     dev = {}

@@ -9,8 +9,9 @@ block.  They are compiled into tmp_path as programs with the reference's release
 reference's filter window misc sched sincospi osc gauss rtp and the oracle's FFT provider (oracle/_build/fftw_shim.o, dft_ref.o); the
 reference's transform runs in the caller's thread (N_worker_threads = 0, for the reason tests/c/ref_packetd_wrap.c gives).
 
-stereod: all five instances of tests/test_gpu_mpx.py's scenario at 1, 5 and 20 ms; rdsd: the RDS test's two instances at 5 ms (its Blocktime
-is a constant); each on the reference's float64 transform and on its float32 one (oracle_fft_set_precision).  EVERY PCM sample:
+stereod: all five instances of tests/test_gpu_mpx.py's scenario at 1, 5 and 20 ms and, for tests/test_gpu_mpx_shapes.py, at 2 and 10 ms;
+rdsd: the RDS test's two instances at 5 ms (its Blocktime is a constant: the RDS pools at 1, 2 and 10 ms rest on the restatement's
+parametrisation by the block time, which stereod's pin holds for the code the two share); each on the reference's float64 transform and on its float32 one (oracle_fft_set_precision).  EVERY PCM sample:
 |pcm - 32767 clamp(y, -1, 1)| <= 1 + 32767 lim, y the restatement's float64 value and lim the block's max-abs limit of rule (A) in
 tests/test_gpu_mpx.py; the recorded states: within lim of the restatement's.  The tests print the worst distance over the allowed, the share
 of bit-equal samples in the last block and the time the reference's loop takes per block.
@@ -91,9 +92,9 @@ def compare(label, pcm, states, ref, lims, olen):
 
 
 @needs_ref
-@pytest.mark.parametrize("shape", list(tg.SHAPES))
+@pytest.mark.parametrize("shape", list(tg.SHAPES) + [0.002, 0.01])       # (2 and 10 ms: the shapes of tests/test_gpu_mpx_shapes.py)
 def test_the_restatement_of_stereod_s_loop_against_stereod_c(refmpx, tmp_path, shape):
-    bt = tg.SHAPES[shape]
+    bt = tg.block_time(shape)
     olen = mo.geometry(bt)["olen"]
     tcs = [75e-6, 50e-6, 0.0, 75e-6, 75e-6]
     for k, blocks in enumerate(tg.scenario(shape)):
