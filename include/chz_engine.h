@@ -128,6 +128,40 @@ int chz_input_raw_check(int in_type, int format, int bits, long n);   /* 0, or <
 int chz_input_write_raw(chz_engine *e, int format, int bits, const void *host_samples, long n, double scale, unsigned *ticket);
 int chz_input_write_raw_device(chz_engine *e, int format, int bits, const void *dev_samples, long n, double scale, unsigned *ticket);
 int chz_input_raw_stats(chz_engine *e, unsigned ticket, unsigned long long *energy, unsigned *clipped_samples, unsigned *clipped_components);
+/* The synthetic front end: sig_gen's sample law (src/sig_gen.c:291-296 REAL, :321-326 COMPLEX; oscillator src/osc.c:28-70, popcount
+ * Gaussian over xoshiro256** src/gauss.c:47-61,95-111) generated on the device straight into the FLOAT ring, so that no samples cross
+ * the link, the input never repeats and every device of a sharded run can make the identical stream by itself.  Sample n of the stream
+ * (0 <= n < 2^53) depends only on the parameters and n:
+ *   REAL     (float)((amplitude cos(2 pi phi_n) + noise g_n) scale)
+ *   COMPLEX  two draws a sample, the real part's first, added to amplitude cis(2 pi phi_n); the ring holds re, im
+ *   phi_n    frac(a n), a the angle of the reference's step phasor for set_osc's argument freq (cycles/sample), the product exact
+ *   g_j      the popcount Gaussian of the generator's j-th output; the generator is seeded as xoshiro256ss_seed seeds it (the
+ *            reference always uses seed 1)
+ * The noise term is the reference's bit for bit.  The carrier is the closed form, evaluated in double at the first sample of every run of
+ * CHZ_SIGGEN_RUN ring floats and rotated from there: the reference's recurrence rounds differently, by up to 1e-10 of the amplitude within
+ * 2^18 samples (a float sample differs by one unit in the last place now and then).
+ * chz_input_siggen_set describes the whole stream and puts the position at sample 0 (set on a running stream restarts it: a change of
+ * parameters with phase continuity is not offered, as sig_gen_tune is not in the reference); _seek / _tell move and read the position.
+ * chz_input_generate appends the next n samples at the ring's write position: a ring write like chz_input_write, with which (and with
+ * chz_input_write_raw) it may alternate on one engine; per call the host advances the generator by one O(1) jump, everything per sample
+ * and per lane happens in the kernel (siggen_fill).  n == 0 is a valid, empty generate.  Refused (-1, nothing enqueued, nothing advanced):
+ * no stream described, an engine in int16 mode, n < 0, n beyond the ring, a position that would pass 2^53, non-finite parameters.
+ *   ticket   out (may be NULL): this generate's number, counted per engine from 0
+ * chz_input_generate_stats: the sum of samp^2 (re^2 + im^2) over the generate, samp the value BEFORE scale (in_energy of sig_gen.c), added
+ * in double in a fixed order (two runs give the same bits); the last CHZ_RAW_TICKETS generates' can be read.  Synchronous on the
+ * engine's stream.
+ * chz_siggen_check / _seed / _jump touch no device: would these parameters be taken; the seeded generator state; state <- T^draws state
+ * for draws = draws_hi 2^64 + draws_lo (T the generator's update, which is linear over GF(2)). */
+#define CHZ_SIGGEN_RUN 64    /* ring floats one lane of the kernel produces from its own generator state */
+typedef struct { double freq, amplitude, noise, scale; unsigned long long seed; } chz_siggen_params;
+int chz_siggen_check(int in_type, const chz_siggen_params *p);
+int chz_siggen_jump(unsigned long long state[4], unsigned long long draws_lo, unsigned long long draws_hi);
+int chz_siggen_seed(unsigned long long seed, unsigned long long state[4]);
+int chz_input_siggen_set(chz_engine *e, const chz_siggen_params *p);
+int chz_input_siggen_seek(chz_engine *e, unsigned long long sample);
+int chz_input_siggen_tell(chz_engine *e, unsigned long long *sample);
+int chz_input_generate(chz_engine *e, long n, unsigned *ticket);
+int chz_input_generate_stats(chz_engine *e, unsigned ticket, double *energy);
 /* direct access to the device ring for HBM-resident benchmarks */
 int chz_input_ring(chz_engine *e, float **dev_ring, long *ring_len_floats);
 /* Re-seat the input ring in front of block `job`: the next L samples written are that block's new samples and `history`

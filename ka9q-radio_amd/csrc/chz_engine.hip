@@ -250,6 +250,7 @@ struct NotchTurn {
 
 #define CHZ_NOTCH_EVENTS 8
 struct WelchBank;                   // chz_welch.inc
+struct SigGenState;                 // chz_siggen.inc
 
 struct chz_engine {
   int L = 0, M = 0, N = 0, in_type = 0, bins = 0, per = 1, device = 0, ring_blocks = 0;
@@ -288,6 +289,7 @@ struct chz_engine {
   RawPart* raw_part = nullptr;                // [CHZ_RAW_TICKETS][CHZ_RAW_MAX_GRID] per-workgroup statistics of the latest writes
   unsigned raw_tickets = 0; int raw_grid[CHZ_RAW_TICKETS] = {};   // writes so far; workgroups of the write in each ticket slot (0: an empty write)
   long wpos = 0;                              // write position (floats)
+  SigGenState* siggen = nullptr;              // the stream chz_input_generate writes (chz_input_siggen_set; chz_siggen.inc)
   float2* spec[CHZ_ND] = {nullptr, nullptr, nullptr, nullptr};
   bool spec_owned[CHZ_ND] = {false, false, false, false};
   // A master length outside the compiled axes runs as Bluestein's chirp-z over a planned complex transform of length Mz >= 2N - 1
@@ -349,6 +351,7 @@ template <class T> static int upload(T** dst, const std::vector<f2>& v) {
 }
 
 static void welch_free_all(chz_engine* e);      // chz_welch.inc
+static void siggen_free(chz_engine* e);         // chz_siggen.inc
 static void welch_bank_gone(chz_engine* e, int bank);      // chz_welch.inc: a channel bank is destroyed, its analysers are detached
 // in front of an input write of n samples at ring position pos: the write waits for an unfinished poll that reads any of them
 static int welch_guard(chz_engine* e, long long pos, long long n) {
@@ -658,6 +661,7 @@ void chz_engine_destroy(chz_engine* e) {
   if (e->welch_s) hipStreamSynchronize(e->welch_s);
   drop_graph(e);
   welch_free_all(e);
+  siggen_free(e);
   for (int i = 0; i < e->nlanes; i++) {
     hipFree(e->lanes[i].buf);
     if (i > 0 && e->lanes[i].s) hipStreamDestroy(e->lanes[i].s);
@@ -2556,3 +2560,4 @@ int chz_run_blocks(chz_engine* e, unsigned job0, int nblocks, int mode, int inst
 #include "chz_ctcss.inc"
 #include "chz_mpx.inc"
 #include "chz_welch.inc"
+#include "chz_siggen.inc"

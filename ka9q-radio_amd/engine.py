@@ -91,9 +91,15 @@ AFSK_FRAME_MAX = 16384
 # chz_input_write_raw: CHZ_RAW_*, and the bytes a sample takes as (bytes, samples)
 RAW_PACKED12, RAW_U16, RAW_S16, RAW_U8, RAW_S8, RAW_S16_IQ, RAW_U8_IQ, RAW_S8_IQ = range(8)
 RAW_BYTES = {RAW_PACKED12: (12, 8), RAW_U16: (2, 1), RAW_S16: (2, 1), RAW_U8: (1, 1), RAW_S8: (1, 1), RAW_S16_IQ: (4, 1), RAW_U8_IQ: (2, 1), RAW_S8_IQ: (2, 1)}
+SIGGEN_RUN = 64          # CHZ_SIGGEN_RUN: ring floats one lane of the generating kernel produces
 PCM_S16BE, PCM_S16LE, PCM_F32LE, PCM_F32BE, PCM_MULAW, PCM_ALAW, PCM_F16LE, PCM_F16BE = 0, 1, 2, 3, 4, 5, 6, 7
 FLAG_NO_SAMPLES, FLAG_MUTE, FLAG_PLL_LOCK, FLAG_TONE_MUTE, FLAG_PENDING = 1, 2, 4, 8, 16
 FRAME_PENDING = 2        # DemodStatus.frame of a filter2 bank's pending block
+
+
+class SigGenParams(C.Structure):
+    """chz_siggen_params: sig_gen's stream (freq in cycles/sample, the argument of set_osc)"""
+    _fields_ = [("freq", C.c_double), ("amplitude", C.c_double), ("noise", C.c_double), ("scale", C.c_double), ("seed", C.c_ulonglong)]
 
 
 # every symbol include/chz_engine.h declares (checked by tests/test_host_logic.py and __graft_entry__.build())
@@ -109,6 +115,8 @@ SYMBOLS = [
     "chz_bank_set_tuning", "chz_bank_read_power", "chz_bank_read_power_async",
     "chz_input_write_i16", "chz_input_write_i16_device", "chz_input_stats",
     "chz_input_raw_check", "chz_input_write_raw", "chz_input_write_raw_device", "chz_input_raw_stats",
+    "chz_siggen_check", "chz_siggen_jump", "chz_siggen_seed", "chz_input_siggen_set", "chz_input_siggen_seek", "chz_input_siggen_tell",
+    "chz_input_generate", "chz_input_generate_stats",
     "chz_bank_enable_noise", "chz_bank_read_noise", "chz_bank_read_noise_async", "chz_bank_create_real", "chz_bank_set_isb", "chz_bank_set_beam",
     "chz_set_notches_alpha", "chz_slot_sync", "chz_engine_check", "chz_input_seek", "chz_input_mark", "chz_input_mark_wait", "chz_engine_notch_order",
     "chz_bank_set_demod", "chz_bank_pcm_stride", "chz_bank_set_pcm_stride", "chz_bank_read_pcm", "chz_bank_read_pcm_async",
@@ -180,6 +188,14 @@ def lib():
         L.chz_input_write_raw.argtypes = [_vp, _i, _i, _vp, _l, _d, C.POINTER(_u)]
         L.chz_input_write_raw_device.argtypes = [_vp, _i, _i, _vp, _l, _d, C.POINTER(_u)]
         L.chz_input_raw_stats.argtypes = [_vp, _u, C.POINTER(C.c_ulonglong), C.POINTER(_u), C.POINTER(_u)]
+        L.chz_siggen_check.argtypes = [_i, C.POINTER(SigGenParams)]
+        L.chz_siggen_jump.argtypes = [C.POINTER(C.c_ulonglong * 4), C.c_ulonglong, C.c_ulonglong]
+        L.chz_siggen_seed.argtypes = [C.c_ulonglong, C.POINTER(C.c_ulonglong * 4)]
+        L.chz_input_siggen_set.argtypes = [_vp, C.POINTER(SigGenParams)]
+        L.chz_input_siggen_seek.argtypes = [_vp, C.c_ulonglong]
+        L.chz_input_siggen_tell.argtypes = [_vp, C.POINTER(C.c_ulonglong)]
+        L.chz_input_generate.argtypes = [_vp, _l, C.POINTER(_u)]
+        L.chz_input_generate_stats.argtypes = [_vp, _u, C.POINTER(_d)]
         L.chz_forward.argtypes = [_vp, _u]
         L.chz_set_notches.argtypes = [_vp, _vp, _i, _d]
         L.chz_set_notches_alpha.argtypes = [_vp, _vp, _vp, _i]
@@ -315,6 +331,23 @@ def _check(r):
     return r
 
 
+def siggen_seed(seed=1):
+    """The generator state sig_gen's stream starts from (xoshiro256ss_seed, src/gauss.c:32-45): four 64-bit words."""
+    st = (C.c_ulonglong * 4)()
+    _check(lib().chz_siggen_seed(int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(st)))
+    return tuple(st)
+
+
+def siggen_jump(state, draws):
+    """The generator state `draws` (< 2^128) outputs after `state`; O(1), touches no device."""
+    draws = int(draws)
+    if not 0 <= draws < 1 << 128:
+        raise ValueError("draws out of range")
+    st = (C.c_ulonglong * 4)(*[int(w) for w in state])
+    _check(lib().chz_siggen_jump(C.byref(st), draws & 0xFFFFFFFFFFFFFFFF, draws >> 64))
+    return tuple(st)
+
+
 def gather_descriptor(in_type, master_bins, P, shift):
     out = (_i * 6)()
     lib().chz_gather_descriptor(in_type, master_bins, P, int(shift), C.byref(out))
@@ -398,6 +431,34 @@ class Engine:
 
     def write_device(self, dev_ptr, n):
         _check(lib().chz_input_write_device(self._h, dev_ptr, n))
+
+    def siggen(self, freq, amplitude, noise, scale, seed=1):
+        """Describe sig_gen's stream (carrier of `freq` cycles/sample and `amplitude`, Gaussian noise of deviation `noise`, all times
+        `scale`); the position goes to sample 0.  generate() then writes it into the ring on the device."""
+        p = SigGenParams(float(freq), float(amplitude), float(noise), float(scale), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        _check(lib().chz_input_siggen_set(self._h, C.byref(p)))
+
+    def siggen_seek(self, sample):
+        if not 0 <= int(sample) < 1 << 64:
+            raise ValueError("sample out of range")
+        _check(lib().chz_input_siggen_seek(self._h, int(sample)))
+
+    def siggen_tell(self):
+        n = C.c_ulonglong(0)
+        _check(lib().chz_input_siggen_tell(self._h, C.byref(n)))
+        return n.value
+
+    def generate(self, n):
+        """Append the stream's next n samples at the ring's write position (asynchronous); returns the generate's ticket."""
+        t = _u(0)
+        _check(lib().chz_input_generate(self._h, int(n), C.byref(t)))
+        return t.value
+
+    def generate_energy(self, ticket):
+        """Sum of samp^2 over generate `ticket`, samp before `scale`; the last 8 generates' can be read."""
+        en = _d(0.0)
+        _check(lib().chz_input_generate_stats(self._h, ticket, C.byref(en)))
+        return en.value
 
     def ring(self):
         p, n = _vp(), _l()
